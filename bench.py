@@ -8,10 +8,15 @@ default DVS parameters (v2e_args.py:150-204), Philox RNG, frames resident in HBM
 One *step* = one second of source video = 300 emulator frames advanced on device with no
 host synchronisation in between; the host prepares and enqueues step s+1 while step s
 executes (EventEmulator.generate_events_batch_async) and then reads step s's records.
-value = events emitted / wall time (Mevents/s), whole job.  The timed region of `--steps K` steps (bracketed by barrier +
-device synchronisation on both sides, max over ranks) is repeated `--blocks` times (default 9) and the MEDIAN block is the
-one reported (`ms_per_step`, `value`), with the spread of the blocks beside it: a 20-step region is 25 ms, and the first
-region after start-up runs a few percent slow.
+value = events emitted / wall time (Mevents/s), whole job.  The `--steps K` timed steps run as consecutive regions (each
+bracketed by barrier + device synchronisation on both sides, max over ranks): up to `--blocks` of them (default 9), none shorter
+than MIN_BLOCK_STEPS steps, K steps in all.  The MEDIAN region is the one reported (`ms_per_step`, `value`), with the spread of
+the regions beside it: the first region after start-up runs a few percent slow.
+
+--dump-outputs DIR: after the timed steps, what the timed path returned for its last step -- the event rows and the per-frame
+event counts a caller of generate_events_batch_async receives -- is written to DIR as float32 / float64 .npy files (a fixed,
+seeded sample of the rows when they exceed DUMP_BUDGET_BYTES).  Inputs are seeded: two builds run with the same arguments can be
+compared output for output.
 
 N > 1 (driver: python -m torch.distributed.run ...): one independent clip per GPU
 (BASELINE.json configs[4]); every step ends with an RCCL all-gather of the ranks' event
@@ -51,6 +56,48 @@ STAMP_STEPS = 20          # steps of the timed loop repeated with the chain's la
 F32_MFMA_PEAK = 157.3e12  # MI355X_MICROARCH.md: f32-input MFMA peak
 INSTR_STEPS = 6           # steps re-run instrumented for the live per-launch kernel times of the roofline object
 CLIP_STEPS = 24           # distinct seconds of synthetic video generated; longer runs cycle through them
+MIN_BLOCK_STEPS = 20      # shortest timed region: each region ends in a device synchronisation that drains the pipelined runs
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: all files together stay below 64 MB
+DUMP_SEED = 1234          # --dump-outputs: seed of the row sample of a larger event stream
+
+
+def dump_outputs(out_dir, ev, counts):
+    """Write the last timed step's outputs: events.npy (float32 [n, 4] rows t, x, y, p, or a sorted seeded sample of them),
+    events_index.npy (float64: which rows the sample holds) and counts.npy (float64: events per frame)."""
+    os.makedirs(out_dir, exist_ok=True)
+    counts = np.asarray(counts.cpu().numpy() if torch.is_tensor(counts) else counts, np.float64).ravel()
+    n = int(ev.shape[0]) if ev is not None else 0
+    cap = max(1, (DUMP_BUDGET_BYTES - 16 * counts.size) // (16 + 8))  # a row: 16 B of events + 8 B of index
+    if n > cap:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=cap, replace=False))
+        rows = ev[torch.from_numpy(idx).to(ev.device)] if torch.is_tensor(ev) else ev[idx]
+    else:
+        idx = np.arange(n)
+        rows = ev[:n] if ev is not None else np.zeros((0, 4), np.float32)
+    rows = np.ascontiguousarray(rows.cpu().numpy() if torch.is_tensor(rows) else rows, np.float32).reshape(-1, 4)
+    np.save(os.path.join(out_dir, "events.npy"), rows)
+    np.save(os.path.join(out_dir, "events_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "counts.npy"), counts)
+    return {"dir": out_dir, "rows": n, "rows_written": int(rows.shape[0]), "frames": int(counts.size)}
+
+
+class _LastStep:
+    """Stands in for the emulator in the timed loop and keeps the handle of the last run enqueued (--dump-outputs); everything else
+    is the emulator's own.  A run's result stays valid until the second-next run is enqueued (generate_events_batch_async)."""
+
+    def __init__(self, emu):
+        import functools
+        self._emu, self.pending = emu, None
+        inner = emu.generate_events_batch_async
+
+        @functools.wraps(inner)  # run_steps inspects the signature
+        def generate_events_batch_async(*a, **k):
+            self.pending = inner(*a, **k)
+            return self.pending
+        self.generate_events_batch_async = generate_events_batch_async
+
+    def __getattr__(self, name):
+        return getattr(self._emu, name)
 
 
 def gen_frames_device(n, seed, device, h=H, w=W, sigma=3.0, i0=0):
@@ -388,7 +435,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--blocks", type=int, default=9, help="timed regions of --steps steps each; the median one is reported")
+    ap.add_argument("--blocks", type=int, default=9,
+                    help="timed regions the --steps steps are split into (each at least %d steps); the median one is reported"
+                         % MIN_BLOCK_STEPS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's event rows and per-frame counts to DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the slomo / batched / frame-API side measurements")
     ap.add_argument("--no-allgather", action="store_true")
@@ -449,14 +500,17 @@ def main():
         return emu
 
     use_gather = (world > 1 or args.force_allgather) and not args.no_allgather
-    nblocks = max(1, args.blocks)
+    nblocks = max(1, min(args.blocks, K // MIN_BLOCK_STEPS))
+    block_steps = [K // nblocks + (1 if b < K % nblocks else 0) for b in range(nblocks)]  # K steps in all
 
     def timed_blocks(emu, gather):
-        """`nblocks` timed regions of K steps each on one emulator (the clip keeps running); every region is bracketed by
-        barrier + synchronize inside run_steps; (seconds, events) per region, seconds = max over ranks."""
+        """The K timed steps as `nblocks` consecutive regions on one emulator (the clip keeps running); every region is bracketed
+        by barrier + synchronize inside run_steps; (seconds, events, steps) per region, seconds = max over ranks."""
         res = []
-        for b in range(nblocks):
-            el, ne = run_steps(emu, frames_all, F, DT, K, Wm if b == 0 else 0, gather, dist, device, first_step=b * K + (Wm if b else 0))
+        first = Wm
+        for b, nb in enumerate(block_steps):
+            el, ne = run_steps(emu, frames_all, F, DT, nb, Wm if b == 0 else 0, gather, dist, device, first_step=first if b else 0)
+            first += nb
             if dist is not None:
                 t = torch.tensor([el], dtype=torch.float64, device=device)
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -464,7 +518,7 @@ def main():
                 n = torch.tensor([ne], dtype=torch.float64, device=device)
                 dist.all_reduce(n, op=dist.ReduceOp.SUM)
                 ne = int(n[0].item())
-            res.append((el, ne))
+            res.append((el, ne, nb))
         return res
 
     def median_block(res):
@@ -476,8 +530,12 @@ def main():
     if use_gather:
         gather = (EventStreamGatherer("cpu", world) if STUB else
                   EventStreamGatherer(device, world, wire=args.gather_wire, algo=args.gather_algo, sensor=(H, W)))
-    blocks = timed_blocks(emu, gather)
-    elapsed, tot_events = median_block(blocks)
+    timed = _LastStep(emu) if args.dump_outputs else emu
+    blocks = timed_blocks(timed, gather)
+    elapsed, tot_events, Km = median_block(blocks)  # Km: the steps of the reported region
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, *timed.pending.result())
     compute_only = None
     if use_gather:  # the same loop without the exchange: how much of the N-GPU number the interconnect decides
         emu_c = make_emu()
@@ -491,10 +549,10 @@ def main():
             "value": round(tot_events / elapsed / 1e6, 3),
             "unit": "Mevents/s",
             "n_gpus": world, "steps": K, "warmup": Wm,
-            "ms_per_step": round(elapsed / K * 1e3, 4),
-            "timed_blocks": {"blocks": nblocks, "steps_each": K, "reported": "median block",
-                             "Mevents_per_s": [round(ne / el / 1e6, 1) for el, ne in blocks],
-                             "spread_rel": round((max(ne / el for el, ne in blocks) - min(ne / el for el, ne in blocks)) /
+            "ms_per_step": round(elapsed / Km * 1e3, 4),
+            "timed_blocks": {"blocks": nblocks, "steps_each": block_steps, "timed_steps": K, "reported": "median block",
+                             "Mevents_per_s": [round(ne / el / 1e6, 1) for el, ne, _ in blocks],
+                             "spread_rel": round((max(ne / el for el, ne, _ in blocks) - min(ne / el for el, ne, _ in blocks)) /
                                                  (tot_events / elapsed), 4)},
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f64", "data": "stub" if STUB else "synthetic",
@@ -505,25 +563,27 @@ def main():
                                    "%d frames/step device-resident, one clip per GPU" % F,
                        "frames_per_step": F, "clips_per_gpu": 1,
                        "event_stream_allgather": bool(use_gather)},
-            "emulator_frames_per_s": round(world * K * F / elapsed, 1),
-            "events_per_frame": round(tot_events / (world * K * F), 1),
+            "emulator_frames_per_s": round(world * Km * F / elapsed, 1),
+            "events_per_frame": round(tot_events / (world * Km * F), 1),
         }
+        if dumped:
+            out["dumped_outputs"] = dumped
         if compute_only:
             out["compute_only"] = {"value": round(compute_only[1] / compute_only[0] / 1e6, 3), "unit": "Mevents/s",
-                                   "ms_per_step": round(compute_only[0] / K * 1e3, 4),
+                                   "ms_per_step": round(compute_only[0] / compute_only[2] * 1e3, 4),
                                    "note": "same loop, no event-stream exchange"}
             out["with_allgather"] = {"value": out["value"], "unit": "Mevents/s",
-                                     "bytes_gathered_per_rank_per_step": int(gather.bytes_gathered / max(nblocks * K + Wm, 1)),
+                                     "bytes_gathered_per_rank_per_step": int(gather.bytes_gathered / max(K + Wm, 1)),
                                      "algo": args.gather_algo,
                                      "wire_format": ("4 B per event + 8 B per block of one time stamp (v2e_events_pack32)"
                                                      if gather.wire == "pack32" else "8 B per event (v2e_events_pack64)")}
 
     # ---------------- roofline of the dominant emulator kernel (rank 0, HIP events, same workload)
     if rank == 0 and not STUB and args.no_roofline_rerun:
-        whole = emulator_bytes_per_pixel(DEFAULT_KW) * H * W + 16 * tot_events / (world * K * F)
+        whole = emulator_bytes_per_pixel(DEFAULT_KW) * H * W + 16 * tot_events / (world * Km * F)
         out["roofline"] = {"bound": "hbm", "kernel": "k_chain", "achieved": None, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": None, "traffic": None,
-                           "whole_step": {"algorithmic_bytes_per_frame": int(whole), "achieved_GBps": round(whole * K * F / elapsed / 1e9, 2),
-                                          "frac": round(whole * K * F / elapsed / HBM_PEAK, 5)},
+                           "whole_step": {"algorithmic_bytes_per_frame": int(whole), "achieved_GBps": round(whole * Km * F / elapsed / 1e9, 2),
+                                          "frac": round(whole * Km * F / elapsed / HBM_PEAK, 5)},
                            "note": "--no-roofline-rerun: no per-launch measurement in this run"}
     if rank == 0 and not STUB and not args.no_roofline_rerun:
         eng = emu._engine
@@ -533,7 +593,7 @@ def main():
         # the emission on their streams beside the chain), every chain launch leaving the device wall-clock time of its first workgroup's
         # start and its last workgroup's end (v2e_emu_launch_stamps: two atomics per workgroup, nothing else changes)
         eng.launch_stamps(STAMP_STEPS)
-        el_st, ne_st = run_steps(emu, frames_all, F, DT, STAMP_STEPS, 0, None, None, device, first_step=Wm + nblocks * K)
+        el_st, ne_st = run_steps(emu, frames_all, F, DT, STAMP_STEPS, 0, None, None, device, first_step=Wm + K)
         st = eng.launch_stamps(0, read=STAMP_STEPS).astype(np.int64)
         nl_st = int((st[0, :, 1] > 0).sum())
         st_us = st[:, :nl_st] / 1e3
@@ -573,7 +633,7 @@ def main():
         # event writer reads.  A launch covers `fpl` frames.
         n_step = max(prof.get("step_launches", 0), 1)   # chain launches of the instrumented steps
         n_per_step = n_step / INSTR_STEPS
-        period_us = elapsed / K / n_per_step * 1e6  # the driver-timed region: one step = n_per_step chain launches
+        period_us = elapsed / Km / n_per_step * 1e6  # the driver-timed region: one step = n_per_step chain launches
         kernel_us = prof["rank"] / n_step * 1e3    # HIP events before and after every chain launch, on its stream: the kernels alone
         # 53 B per pixel and frame x the frames a launch advances ON AVERAGE: a step's launches are full ones (fpl
         # frames), one partial one and the tail launch that only validates, and all of them are in the average duration
@@ -638,12 +698,12 @@ def main():
                              "frac": round(step_bytes / (period_us * 1e-6) / HBM_PEAK, 5),
                              "note": "the same bytes against the timed region's time per chain launch (ms_per_step / launches per step: "
                                      "everything the step does -- k_ahead, the emission kernels, gaps, redo passes -- included)"},
-            "instruction_issue": instruction_issue(elapsed / (K * F) * 1e3),
+            "instruction_issue": instruction_issue(elapsed / (Km * F) * 1e3),
             "event_writer_us_per_batch": round(prof["emit"] / max(prof.get("emit_batches", 1), 1) * 1e3, 3),
             "emission": {"frames_per_batch": fpb, "algorithmic_bytes_per_frame": int(emit_bytes)},
             "whole_step": {"algorithmic_bytes_per_frame": int(whole),
-                           "achieved_GBps": round(whole * K * F / elapsed / 1e9, 2),
-                           "frac": round(whole * K * F / elapsed / HBM_PEAK, 5)},
+                           "achieved_GBps": round(whole * Km * F / elapsed / 1e9, 2),
+                           "frac": round(whole * Km * F / elapsed / HBM_PEAK, 5)},
             "note": "algorithmic bytes = 53 B x pixels x the step's frames / the step's chain launches (what a launch advances on average; "
                     "SURVEY.md 8(d)).  Three durations divide them: timed_configuration (what `frac` is: live device stamps of the timed "
                     "loop), alone_hip_events (live HIP events, each kernel alone), as_delivered (the driver-timed region per launch).  The "

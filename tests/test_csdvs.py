@@ -1,8 +1,8 @@
 """The centre-surround DVS (cs_lambda_pixels; emulator.py:245-272, 707-716, 753-754, 1061-1124).
 
 CPU: the oracle's restatement of `_update_csdvs`'s stepping loop against the reference's digests (csdvs_steps.npz: all
-num_steps steps, and loops that end early on max_change <= 1e-5; float32 and float64 state) and, where the reference tree is
-present, against the live reference on fresh planes.
+num_steps steps, and loops that end early on max_change <= 1e-5; float32 and float64 state) and against the reference's
+`_update_csdvs` on fresh DAVIS346 planes (reference_cases.npz).
 GPU: k_cs_step (v2e_csdvs_update) against the same digests and against the oracle on odd sizes (edges, partial blocks,
 one-row and one-column planes) bit for bit; the drop-in class with cs_lambda_pixels against reference-generated fixtures --
 bit for bit at DAVIS346 (float64 and float32 state: the reference's convolution sums in the order the kernel fixes), and within
@@ -34,31 +34,30 @@ def test_oracle_stepping_loop_matches_reference_digests(name, oracle_lib):
         assert last <= STOP and steps < int(z[name + "_num_steps"])
 
 
-@pytest.mark.parametrize("dt", [np.float32, np.float64])
-def test_oracle_stepping_loop_equals_live_reference(dt, oracle_lib):
-    import ref_harness as rh
-    if not rh.reference_available():
-        pytest.skip("reference tree not present")
-    import logging
-    import torch
-    logging.disable(logging.CRITICAL)
-    torch.set_num_threads(1)
-    EE = rh.ref_emulator_cls()
+def stepping_loop_case(dt):
+    """Fresh planes at DAVIS346 and the emulator parameters of the stepping-loop cross-check: (p, h0, lambda, tau_p_ms, dt_frame)."""
     rng = np.random.default_rng(77)
     H, W = 260, 346  # the reference's float32 conv sum is in kernel order from 200 x 200 up (make_golden_csdvs.py)
     p = (rng.standard_normal((H, W)) * 0.3 + 2).astype(dt)
     h0 = (p + rng.standard_normal((H, W)) * 0.02).astype(dt)
-    lam, tau_p_ms, delta_time = 4.0, 3.0, 1 / 250
-    ref = EE(seed=1, device="cpu", cs_lambda_pixels=lam, cs_tau_p_ms=tau_p_ms)
-    ref.lp_log_frame, ref.cs_surround_frame = torch.from_numpy(p.copy()), torch.from_numpy(h0.copy())
-    ref._update_csdvs(delta_time)
+    return p, h0, 4.0, 3.0, 1 / 250
+
+
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+def test_oracle_stepping_loop_equals_live_reference(dt, oracle_lib):
+    """The reference's `_update_csdvs` on these planes, as tests/golden/make_golden_reference_cases.py recorded it
+    (reference_cases.npz: steps taken and the surround plane's digest)."""
+    from test_oracle_vs_reference import digest, reference_cases
+    ref = reference_cases()
+    key = "csdvs_loop_" + np.dtype(dt).name
+    p, h0, lam, tau_p_ms, delta_time = stepping_loop_case(dt)
     tau_p, tau_h = tau_p_ms * 1e-3, (tau_p_ms / lam ** 2) * 1e-3
     num_steps = int(np.ceil((delta_time / min(tau_p, tau_h)) * 5))
     adt = delta_time / num_steps
     h = h0.copy()
     steps, _ = oracle_lib.csdvs_update(p, h, adt / tau_p, adt / tau_h, num_steps, STOP)
-    assert steps == ref.cs_steps_taken[-1]
-    assert np.array_equal(h, ref.cs_surround_frame.numpy())
+    assert steps == int(ref[key + "_steps"])
+    assert digest(h) == str(ref[key + "_sha"])
 
 
 def _device_update(p, h0, alpha_p, alpha_h, num_steps):

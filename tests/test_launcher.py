@@ -108,6 +108,9 @@ def test_v2e_main_with_the_cli_defaults_reaches_the_first_device_call(tmp_path, 
     built = {}
     try:
         v2e = bind(rh.REF_ROOT)
+        # v2e_args.write_args_info names its info file after __main__.__file__: the script a user starts (v2e.py, or the
+        # launcher module) has one; an interpreter that runs pytest without a script file does not
+        monkeypatch.setattr(sys.modules["__main__"], "__file__", v2e.__file__, raising=False)
         cv2 = sys.modules["cv2"]
         for k, v in dict(VideoCapture=_FakeCapture, CAP_PROP_FPS="fps", CAP_PROP_FRAME_COUNT="count", CAP_PROP_FRAME_WIDTH="w",
                          CAP_PROP_FRAME_HEIGHT="h", CAP_PROP_MONOCHROME="mono").items():
