@@ -233,41 +233,36 @@ int v2e_emu_frame(v2e_emu *h, const v2e_emu_params *p, const void *frame, int fr
  * handle's own buffer as before (*events_host says which).  NULL / 0 cancels. */
 int v2e_emu_frame_host_rows(v2e_emu *h, float *pinned_rows, uint64_t cap_rows);
 
+/* v2e_emu_run flags (an OR of these; the low two bits are one of 0 plain launches, V2E_RUN_GRAPH, V2E_RUN_PROFILE). */
+#define V2E_RUN_GRAPH 1                  /* capture the run into a hipGraph, cached while everything baked into it is unchanged */
+#define V2E_RUN_PROFILE 2                /* instrumented and blocking: see v2e_emu_last_profile */
+#define V2E_RUN_PER_FRAME_KERNELS 16     /* count / rank / scan / emit one frame at a time instead of k_chain (also what photoreceptor
+                                            noise, SCIDVS, CSDVS, float64 log frames and > 1024 events per pixel and frame always run) */
+#define V2E_RUN_ONE_FRAME_PER_LAUNCH 128 /* k_chain with one frame per launch (clips whose refractory rule is active on most frames) */
+#define V2E_RUN_REQUIRE_CHAIN 256        /* k_chain or an error where it cannot run */
+#define V2E_RUN_PIPELINED 1024           /* plain launches only: consecutive runs overlap (below) */
+#define V2E_RUN_FRAMES_RESIDENT 2048     /* with V2E_RUN_PIPELINED: nothing enqueued on `stream` still writes `frames` */
+
 /*
  * Philox-mode, fully device-resident multi-frame run: frames [n_frames][n_clips][H*W],
  * t_prev/t_frame host arrays [n_frames][n_clips].  Records for frame f go to
- * recs_dev[f][clip] (device, caller-owned).  No host synchronisation inside.
- * use_graph, low two bits: 0 plain launches, 1 capture the launch sequence into a hipGraph
- * (cached while every baked-in pointer/size is unchanged), 2 instrumented (see
- * v2e_emu_last_profile).  Pipeline: k_chain -- K frames per launch with the per-pixel state in
- * registers (32 on small grids and without a refractory period, 8 on large grids where the
- * refractory rule may force a redo, 1 where a clip's workgroups cannot be co-resident), the rule-off
- * speculation of a launch validated (and redone from a checkpoint on a miss) by the next launch --
- * with the event list built behind it in batches (k_ctot, k_cframe, k_cemit) on a second stream that
- * joins `stream` before the call's work ends; on small grids the state-independent part of every
- * frame (lin-log, low-pass coefficient, Philox draws, leak step, shot decisions) is precomputed by
- * k_ahead on a third.  |128: one frame per launch (clips on which the refractory rule is active on
- * most frames).  |16 selects the unfused count/rank/scan/emit kernels, one frame at a time (kept for
- * A/B measurements; also what runs photoreceptor noise, float64 log-encoded frames and more than
- * 1024 events per pixel and frame); |256 insists on k_chain (error where it cannot run).  All give
- * identical results.
- * Round 5: the run's frame scalars, first frame index and the ADDRESS of `frames` reach the device through one small kernel that
- * reads a pinned staging set (no copy-engine transfer), and the k_chain pipeline's kernels read the frames through that device
- * variable: with use_graph & 1 a cached graph is replayed over whatever `frames` buffer a call names (events / recs_dev are still
- * baked in: callers alternate between fixed buffer sets), so a caller need not copy frames into one fixed buffer per run.
- * Round 6, PIPELINED RUNS (use_graph = 0 | 1024; wherever the k_chain pipeline runs): plain launches on four streams, no
- * graph and no join at the run's end.  `stream` carries the chain's launches and nothing else, so consecutive runs' chains follow one
- * another in one hardware queue; the run's upload, zero fills and k_ahead records go to a stream of the handle that runs ahead of the
- * chain (beside the run before; one k_ahead launch and one wait per run where the handle's ring of frame slots holds the whole run), the
- * emission's tables and rows to two more that finish beside the run after; everything two runs in flight would share exists twice.  `stream` then orders the PIXEL STATE only: the run's event rows and records are complete behind v2e_emu_run_wait
- * (host) / v2e_emu_run_join (a stream), which the caller must call before reading them; every other entry point of the handle joins by
- * itself.  Callers alternate two sets of `events` / `recs_dev` buffers (a run that names the buffers of the run before it waits for that
- * run).  | 2048: the caller vouches that `frames` are resident (nothing enqueued on `stream` still writes them): the run's head then
- * does not wait for `stream`, i.e. for the chain of the run before.  Results are identical to every other mode.
+ * recs_dev[f][clip] (device, caller-owned).  No host synchronisation inside.  Every mode gives identical results.
+ * The k_chain pipeline (K frames per launch, the per-pixel state in registers, the event list built behind it in batches on
+ * streams of the handle) runs wherever it can; otherwise the per-frame kernels.  The pipeline reads the run's frame scalars, first
+ * frame index and the ADDRESS of `frames` from device variables the run's upload fills: a cached graph is replayed over whatever
+ * `frames` buffer a call names, while `events` / `recs_dev` are baked in (callers alternate between fixed buffer sets).
+ * Without V2E_RUN_PIPELINED the run's work is complete on `stream` when it ends there.
+ * PIPELINED runs (V2E_RUN_PIPELINED with plain launches, wherever k_chain runs): `stream` carries the chain's launches and nothing
+ * else, so it orders the PIXEL STATE only; the run's upload, zero fills and k_ahead records go to a stream of the handle that runs
+ * ahead of the chain, the emission's tables and rows to two more that finish beside the run after.  The run's event rows and records
+ * are complete behind v2e_emu_run_wait (host) / v2e_emu_run_join (a stream), which the caller must call before reading them; every
+ * other entry point of the handle joins by itself.  Everything two runs in flight would share exists twice: callers alternate two
+ * sets of `events` / `recs_dev` buffers (a run that names the buffers of the run before it waits for that run).  With
+ * V2E_RUN_FRAMES_RESIDENT the run's head does not wait for `stream`, i.e. for the chain of the run before.
  */
 int v2e_emu_run(v2e_emu *h, const v2e_emu_params *p, const void *frames, int dtype, int n_frames,
                 const double *t_prev, const double *t_frame, uint32_t frame_idx0, float *events,
-                uint64_t cap, v2e_frame_rec *recs_dev, int use_graph, void *stream);
+                uint64_t cap, v2e_frame_rec *recs_dev, int flags, void *stream);
 /* `stream` waits (device side, no host block) for every piece of every pipelined run enqueued on the handle so far. */
 int v2e_emu_run_join(v2e_emu *h, void *stream);
 /* The scratch set (0 / 1) the run enqueued last took if the library enqueued it in pieces (the ticket of that run, valid until the
@@ -283,7 +278,7 @@ const v2e_frame_rec *v2e_emu_run_recs(v2e_emu *h, int ticket, uint64_t *n_recs);
  * k_chain pipeline (a HIP event before and after every chain launch, on its stream): ms_count = first
  * launch's start to last launch's end (gaps included), ms_rank = the sum of the chain kernels' own
  * durations, ms_emit = the k_cemit launches (v2e_emu_last_profile_pipe), ms_scan 0;
- * |16: k_count, k_rank, k_scan, k_emit (a hipEvent before every launch). */
+ * V2E_RUN_PER_FRAME_KERNELS: k_count, k_rank, k_scan, k_emit (a hipEvent before every launch). */
 int v2e_emu_last_profile(v2e_emu *h, double *ms_count, double *ms_rank, double *ms_scan,
                          double *ms_emit, int *launches);
 

@@ -35,6 +35,15 @@ def test_struct_layouts_match_header():
     assert C.sizeof(ConvDesc) == 40 and ConvDesc.weight_s3.offset == 32  # two pointers, 3 ints + pad, split-bf16 weights
 
 
+def test_run_flags_match_header():
+    from v2e_amd import _capi
+    src = open(os.path.join(ROOT, "include", "v2e_amd.h")).read()
+    header = {k: int(v) for k, v in re.findall(r"^#define V2E_(RUN_[A-Z_]+) (\d+)\b", src, flags=re.M)}
+    python = {k: v for k, v in vars(_capi).items() if k.startswith("RUN_")}
+    assert len(header) == 7 and header == python
+    assert (header["RUN_GRAPH"], header["RUN_PROFILE"], header["RUN_PIPELINED"]) == (1, 2, 1024)  # bench.py passes these values
+
+
 def test_emulator_constructor_surface():
     import inspect
     from v2e_amd import EventEmulator

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from fixtures import PHILOX_HD_FIXTURES, PhiloxFixture, sha
+from v2e_amd._capi import RUN_GRAPH, RUN_REQUIRE_CHAIN
 
 pytestmark = pytest.mark.gpu
 
@@ -80,7 +81,7 @@ def test_chain_records_built_in_kernel_on_small_grids(name, chain_k, monkeypatch
     monkeypatch.setenv("V2E_AMD_CHAIN_FUSED", "1")
     monkeypatch.setenv("V2E_AMD_CHAIN_K", str(chain_k))
     fx = PhiloxFixture(name)
-    for use_graph in (256, 257):
+    for use_graph in (RUN_REQUIRE_CHAIN, RUN_REQUIRE_CHAIN | RUN_GRAPH):
         emu = _mk(fx, seed=fx.seed, rng_mode="philox")
         ev, counts = emu.generate_events_batch(fx.frames, fx.times, use_graph=use_graph)
         _check_clip(fx, emu, ev, counts)
@@ -92,7 +93,7 @@ def test_hd_clip_through_ahead_records(monkeypatch):
     monkeypatch.setenv("V2E_AMD_CHAIN_FUSED", "0")
     fx = PhiloxFixture("philox_noisy_1280x720_long")
     emu = _mk(fx, seed=fx.seed, rng_mode="philox")
-    ev, counts = emu.generate_events_batch(fx.frames[:70], fx.times[:70], use_graph=257, cap=8_000_000)
+    ev, counts = emu.generate_events_batch(fx.frames[:70], fx.times[:70], use_graph=RUN_REQUIRE_CHAIN | RUN_GRAPH, cap=8_000_000)
     assert list(counts) == list(fx.n_events[:70])
     row = 0
     for k, n in enumerate(counts):
@@ -114,7 +115,7 @@ def test_mid_size_sensor_fused_chain_with_refractory(refr, oracle_lib):
     kw = dict(pos_thres=.2, neg_thres=.2, sigma_thres=.03, cutoff_hz=200, leak_rate_hz=.2, shot_noise_rate_hz=1.0,
               refractory_period_s=refr)
     emu = EventEmulator(device="cuda", seed=3, rng_mode="philox", **kw)
-    ev, counts = emu.generate_events_batch(frames, times, use_graph=257)
+    ev, counts = emu.generate_events_batch(frames, times, use_graph=RUN_REQUIRE_CHAIN | RUN_GRAPH)
     assert emu._engine.last_pipeline()[0] == "k_chain(fused records)"
     ora = oracle_lib.OracleEmulator(seed=3, rng_mode="philox", **kw)
     oev = [ora.generate_events(f, t) for f, t in zip(frames, times)]
@@ -258,7 +259,7 @@ def test_chain_carries_lp_without_cutoff_or_shot(shape, nframes, oracle_lib):
     kw = dict(pos_thres=.2, neg_thres=.2, sigma_thres=.03, cutoff_hz=0, leak_rate_hz=.2, shot_noise_rate_hz=0.0,
               refractory_period_s=0.002)
     emu = EventEmulator(device="cuda", seed=5, rng_mode="philox", **kw)
-    ev, counts = emu.generate_events_batch(frames, times, use_graph=257)
+    ev, counts = emu.generate_events_batch(frames, times, use_graph=RUN_REQUIRE_CHAIN | RUN_GRAPH)
     assert emu._engine.last_pipeline()[0].startswith("k_chain")
     ora = oracle_lib.OracleEmulator(seed=5, rng_mode="philox", **kw)
     oev = [ora.generate_events(f, t) for f, t in zip(frames, times)]

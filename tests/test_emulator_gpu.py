@@ -9,6 +9,7 @@ import torch
 from fixtures import (PHILOX_FIXTURES, TAPE_FIXTURES, TAPE_LIVE_FIXTURES, TAPE_PORTABLE_FIXTURES, LiveTapeFixture, PhiloxFixture,
                       PortableTapeFixture, TapeFixture, require_same_generator,
                       events_equal, sha)
+from v2e_amd._capi import RUN_GRAPH, RUN_ONE_FRAME_PER_LAUNCH, RUN_PER_FRAME_KERNELS, RUN_REQUIRE_CHAIN
 
 pytestmark = pytest.mark.gpu
 
@@ -119,9 +120,9 @@ def test_hip_philox_frame_api_matches_reference(name):
     assert [emu.num_events_total, emu.num_events_on, emu.num_events_off] == list(fx.counters)
 
 
-# use_graph: low bits 0 plain launches / 1 hipGraph; no pipeline bit: k_chain (K frames per launch, state in registers)
-# wherever it can run, |256 insists on it, |128 one frame per launch; |16 the unfused count/rank/scan/emit kernels
-PIPELINES = [0, 1, 256, 257, 128, 129, 16, 17]
+# use_graph: 0 plain launches / RUN_GRAPH; no pipeline flag: k_chain (K frames per launch, state in registers) wherever it can run
+PIPELINES = [0, RUN_GRAPH, RUN_REQUIRE_CHAIN, RUN_REQUIRE_CHAIN | RUN_GRAPH, RUN_ONE_FRAME_PER_LAUNCH, RUN_ONE_FRAME_PER_LAUNCH | RUN_GRAPH,
+             RUN_PER_FRAME_KERNELS, RUN_PER_FRAME_KERNELS | RUN_GRAPH]
 
 
 @pytest.mark.parametrize("use_graph", PIPELINES)
@@ -145,7 +146,7 @@ def test_hip_philox_device_resident_clip_matches_reference(name, use_graph):
     assert [emu.num_events_total, emu.num_events_on, emu.num_events_off] == list(fx.counters)
 
 
-@pytest.mark.parametrize("use_graph", [True, 0, 1, 16, 17])
+@pytest.mark.parametrize("use_graph", [True, 0, RUN_GRAPH, RUN_PER_FRAME_KERNELS, RUN_PER_FRAME_KERNELS | RUN_GRAPH])
 def test_hip_philox_device_resident_photoreceptor_noise(use_graph):
     """photoreceptor_noise=True (emulator.py:694-703) in the device-resident API: the noise plane lives in HBM across the
     run (and across runs: the clip is fed in two pieces), events and state equal the reference-generated fixture."""
@@ -169,7 +170,7 @@ def test_hip_philox_device_resident_photoreceptor_noise(use_graph):
     assert sha(st["lp_log_frame"]) == fx.lp_sha
     assert [emu.num_events_total, emu.num_events_on, emu.num_events_off] == list(fx.counters)
     with pytest.raises(V2EAmdError):  # the chain pipelines do not carry the noise plane: refused, not silently noiseless
-        emu.generate_events_batch(fx.frames[-2:], [fx.times[-1] + 0.01, fx.times[-1] + 0.02], use_graph=257)
+        emu.generate_events_batch(fx.frames[-2:], [fx.times[-1] + 0.01, fx.times[-1] + 0.02], use_graph=RUN_REQUIRE_CHAIN | RUN_GRAPH)
 
 
 def test_scidvs_replays_reference_tape(oracle_lib):
@@ -217,7 +218,7 @@ def test_scidvs_philox_matches_reference(api):
     assert np.max(np.abs(hp - z["scidvs_highpass_final"])) <= 1e-12 * max(1.0, np.max(np.abs(z["scidvs_highpass_final"])))
     if api == "clip":
         with pytest.raises(V2EAmdError):  # k_chain does not carry the SCIDVS planes: refused, not silently a plain DVS
-            emu.generate_events_batch(fx.frames[-2:], [fx.times[-1] + 0.01, fx.times[-1] + 0.02], use_graph=257)
+            emu.generate_events_batch(fx.frames[-2:], [fx.times[-1] + 0.01, fx.times[-1] + 0.02], use_graph=RUN_REQUIRE_CHAIN | RUN_GRAPH)
 
 
 def test_scidvs_float32_state_replays_reference_tape(oracle_lib):
@@ -273,7 +274,7 @@ def test_chain_launch_lengths_and_ring_wrap(name, chain_k, monkeypatch):
     monkeypatch.setenv("V2E_AMD_CHAIN_K", str(chain_k))
     monkeypatch.setenv("V2E_AMD_CHAIN_M", "1")  # emission batches of K frames: a ring of 3 K slots
     fx = PhiloxFixture(name)
-    for use_graph in (256, 257):
+    for use_graph in (RUN_REQUIRE_CHAIN, RUN_REQUIRE_CHAIN | RUN_GRAPH):
         emu = _mk(fx, seed=fx.seed, rng_mode="philox")
         ev, counts = emu.generate_events_batch(fx.frames, fx.times, use_graph=use_graph)
         assert list(counts) == list(fx.n_events)
@@ -300,7 +301,7 @@ def test_event_writer_variants_write_the_same_rows(name, variant, monkeypatch):
     else:
         monkeypatch.setenv("V2E_AMD_PULL_TWO_LEVEL", "1")
     fx = PhiloxFixture(name)
-    for use_graph in (256, 257):
+    for use_graph in (RUN_REQUIRE_CHAIN, RUN_REQUIRE_CHAIN | RUN_GRAPH):
         emu = _mk(fx, seed=fx.seed, rng_mode="philox")
         ev, counts = emu.generate_events_batch(fx.frames, fx.times, use_graph=use_graph)
         assert list(counts) == list(fx.n_events)
@@ -328,7 +329,7 @@ def test_event_writer_variants_many_iterations(variant, oracle_lib, monkeypatch)
     ora = oracle_lib.OracleEmulator(rng_mode="philox", seed=21, **kw)
     ref = np.concatenate([e for e in (ora.generate_events(f, t) for f, t in zip(frames, times)) if e is not None])
     hip = EventEmulator(device="cuda", rng_mode="philox", seed=21, max_iters=1024, **kw)
-    ev, counts = hip.generate_events_batch(np.stack(frames), times, use_graph=257, cap=6_000_000)
+    ev, counts = hip.generate_events_batch(np.stack(frames), times, use_graph=RUN_REQUIRE_CHAIN | RUN_GRAPH, cap=6_000_000)
     assert np.array_equal(ev, ref)
 
 
@@ -345,7 +346,7 @@ def test_pipelines_agree_on_benchmark_clip(refr, oracle_lib):
     kw = dict(pos_thres=.2, neg_thres=.2, sigma_thres=.03, cutoff_hz=300, leak_rate_hz=.01, shot_noise_rate_hz=.001,
               refractory_period_s=refr)
     ref = None
-    for use_graph in (257, 129, 17):  # k_chain 32 frames per launch, one frame per launch, count/rank/scan/emit
+    for use_graph in (RUN_REQUIRE_CHAIN | RUN_GRAPH, RUN_ONE_FRAME_PER_LAUNCH | RUN_GRAPH, RUN_PER_FRAME_KERNELS | RUN_GRAPH):  # (32 frames per launch)
         emu = EventEmulator(device="cuda", seed=1, rng_mode="philox", **kw)
         ev, counts = emu.generate_events_batch(frames, times, use_graph=use_graph)
         st = (sha(ev), list(counts), sha(emu.base_log_frame.cpu().numpy()), sha(emu.timestamp_mem.cpu().numpy()),
@@ -555,7 +556,7 @@ def test_many_iterations_grow_scratch(oracle_lib):
     assert ora.last["M"] > 64
 
 
-@pytest.mark.parametrize("use_graph", [257, 129, 17])
+@pytest.mark.parametrize("use_graph", [RUN_REQUIRE_CHAIN | RUN_GRAPH, RUN_ONE_FRAME_PER_LAUNCH | RUN_GRAPH, RUN_PER_FRAME_KERNELS | RUN_GRAPH])
 @pytest.mark.parametrize("refr", [0.0, 0.0004])
 def test_device_resident_clip_many_iterations(use_graph, refr, oracle_lib):
     """> 31 events per pixel per frame: several 64-key chunks in k_ctot, many iterations in k_cpull, refractory on/off."""

@@ -12,6 +12,14 @@ LIB_PATH = os.environ.get("V2E_AMD_LIB") or os.path.join(_HERE, "csrc", "libv2e_
 DT_U8, DT_F32, DT_F64 = 0, 1, 2
 RNG_TAPE, RNG_PHILOX = 0, 1
 FLAG_EVENTS_DROPPED, FLAG_ITERS_CLAMPED, FLAG_SYNC_TIMEOUT = 1, 2, 4
+# v2e_emu_run flags (V2E_RUN_* in include/v2e_amd.h)
+RUN_GRAPH = 1
+RUN_PROFILE = 2
+RUN_PER_FRAME_KERNELS = 16
+RUN_ONE_FRAME_PER_LAUNCH = 128
+RUN_REQUIRE_CHAIN = 256
+RUN_PIPELINED = 1024
+RUN_FRAMES_RESIDENT = 2048
 
 
 class EmuParams(C.Structure):

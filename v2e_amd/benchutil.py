@@ -28,7 +28,7 @@ def run_steps(emu, frames_all, F, dt, steps, warmup, gather, dist, device, first
     gc.freeze()
     nclip = max((int(frames_all.shape[0]) - 1) // F, 1)
     import inspect
-    # The loop's mode: pipelined runs (plain launches on four streams, consecutive runs overlapping: v2e_emu_run 0 | 1024; the clip was
+    # The loop's mode: pipelined runs (plain launches on four streams, consecutive runs overlapping: v2e_emu_run RUN_PIPELINED; the clip was
     # generated and synchronised before the loop, so the frames are resident).  V2E_AMD_BENCH_UG=1: one hipGraph per run, run after
     # run on one stream (rounds 2-5), for A/B.  (The CPU tests' stand-ins have no such switch.)
     ug = int(os.environ.get("V2E_AMD_BENCH_UG", "0"))
@@ -220,6 +220,7 @@ def unet_algorithmic_bytes(n, cin, cout, h, w):
 
 def batched_emulator_bench(device, n_clips=64, frames=60, H=260, W=346):
     """Same emulator kernels, `n_clips` independent 346x260 clips advanced per launch."""
+    from . import _capi
     from .emulator import EventEmulator
     from .engine import EmuEngine
     kw = dict(pos_thres=.2, neg_thres=.2, sigma_thres=.03, cutoff_hz=300, leak_rate_hz=.01,
@@ -252,7 +253,7 @@ def batched_emulator_bench(device, n_clips=64, frames=60, H=260, W=346):
         t_prev = np.array([[(k * frames + j) * dt] * n_clips for j in range(frames)])
         t_frame = t_prev + dt
         eng.run(P, frames_run, t_prev, t_frame, 1 + k * frames, evs[k & 1], recs[k & 1], use_graph=ug)
-        ticket = eng.run_ticket() if (ug & 1024) else -1
+        ticket = eng.run_ticket() if (ug & _capi.RUN_PIPELINED) else -1
         if ticket >= 0:  # pipelined: the library hands the records over itself (v2e_emu_run_wait / _run_recs)
             return k & 1, ticket
         done = torch.cuda.Event()

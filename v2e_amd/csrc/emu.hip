@@ -791,6 +791,44 @@ static inline hipError_t zero_async(void *p, size_t bytes, hipStream_t s)
 }
 
 // =================================================================== host side
+// Everything a pipelined run's head (upload, zero fills, first records), its chain and its last emission batches touch while the run
+// before / after it is still in flight: the handle holds two sets (v2e_emu::sets).  Not here: the pixel state and its ping-pong set,
+// the checkpoints -- only the chain touches them, and chains never overlap.
+struct RunScratch {
+    FrameCtl *run_ctl = nullptr;                // device [run_cap][n_clips]
+    uint32_t *run_fidx = nullptr;               // device: frame_idx0 of the run
+    const void **run_frames = nullptr;          // device: the run's frames (k_ahead / k_chain read the pointer from here)
+    unsigned long long **stamp_slot = nullptr;  // device: the run's slot of launch stamps (nullptr: off), read by k_chain
+    unsigned long long *run_off = nullptr;      // [run_off_cap][n_clips] event offset at the start of every emission batch of the run
+    // sized by the chain configuration (K, E, keys; v2e_emu::ch_*)
+    uint32_t *ch_gM = nullptr;      // [ch_launch_cap][ch_K + 1][n_clips][ch_K]
+    unsigned *ch_bar = nullptr;     // [ch_launch_cap][2 ch_K][n_clips]: one counter per rendezvous of a launch (passes + lock-step frames)
+    uint4 *ch_rec = nullptr;        // [ch_D][n_clips][npx_pad] k_ahead's per-(frame, pixel) records
+    uint32_t *ch_cnt = nullptr;     // [ch_D][n_clips][npx_pad]
+    uint32_t *ch_ruleM = nullptr;   // [ch_D][n_clips]
+    float *ch_tsold = nullptr;      // [ch_D][n_clips][npx_pad] (refractory runs)
+    uint16_t *ch_wmax = nullptr;    // [3][ch_E][n_clips][ch_nwp]
+    uint16_t *ch_wtot = nullptr;    // [3][ch_E][n_clips][nkeys_cap][ch_nwp]
+    CFrame *ch_cf = nullptr;        // [3][ch_E][n_clips]
+    unsigned *ch_cdone = nullptr;   // [3][ch_E][n_clips] k_cframe's per-frame completion counters
+    uint32_t *ch_cT = nullptr, *ch_ckbase = nullptr, *ch_cperm = nullptr, *ch_cpre = nullptr;
+    uint32_t *ch_cmask = nullptr;   // the pull's per-(group, key) pixel ballots (CEmitArgs::cmask), three sets like the other tables
+    uint32_t *ch_cpre16 = nullptr;  // every 16th entry of ch_cpre (CEmitArgs::cpre16)
+    // what the chain configuration sizes
+    void free_chain()
+    {
+        auto drop = [](auto *&b) { hipFree((void *)b); b = nullptr; };
+        drop(ch_gM); drop(ch_bar); drop(ch_rec); drop(ch_cnt); drop(ch_ruleM); drop(ch_tsold); drop(ch_wmax); drop(ch_wtot);
+        drop(ch_cf); drop(ch_cdone); drop(ch_cT); drop(ch_ckbase); drop(ch_cperm); drop(ch_cpre); drop(ch_cmask); drop(ch_cpre16);
+    }
+    void free_all()
+    {
+        free_chain();
+        auto drop = [](auto *&b) { hipFree((void *)b); b = nullptr; };
+        drop(run_ctl); drop(run_fidx); drop(run_frames); drop(stamp_slot); drop(run_off);
+    }
+};
+
 struct v2e_emu {
     int H, W, n_clips, max_iters, device;
     int npx, nwaves, nkeys_cap;
@@ -836,20 +874,16 @@ struct v2e_emu {
     uint64_t fr_ev_cap = 0, fr_est = 0;
     unsigned long long *off_zero = nullptr; // [n_clips] zeros
     // multi-frame run
-    FrameCtl *run_ctl = nullptr;       // device [run_cap][n_clips]
     FrameCtl *run_ctl_host2[2] = {nullptr, nullptr}; // pinned staging, two sets
     hipEvent_t ev_stage[2] = {nullptr, nullptr};
     int run_stage = 0;
     int run_cap = 0;
-    uint32_t *run_fidx = nullptr;      // device: frame_idx0 of the current run
-    uint32_t *run_fidx_host = nullptr; // pinned
-    const void **run_frames = nullptr;      // device: the current run's frames (k_ahead / k_chain read the pointer from here)
+    uint32_t *run_fidx_host = nullptr;      // pinned, two slots (the staging of RunScratch::run_fidx)
     const void **run_frames_host = nullptr; // pinned, two slots
     // per-launch device time stamps of the chain kernel (v2e_emu_launch_stamps): [runs_cap][STAMP_LAUNCHES][2] wall-clock words
     unsigned long long *stamps = nullptr;
     int stamps_runs = 0;                       // runs the buffer holds (0: off)
     unsigned long long stamp_seq = 0;          // runs stamped so far
-    unsigned long long **stamp_slot = nullptr;      // device: the current run's slot (nullptr: off), read by k_chain
     unsigned long long **stamp_slot_host = nullptr; // pinned, two slots
     // captured runs, keyed by everything baked into them (buffers, sizes, parameters): a caller that alternates between two
     // sets of frame / event / record buffers (the asynchronous API) replays two graphs
@@ -863,24 +897,17 @@ struct v2e_emu {
     }
     unsigned long long *dbg = nullptr; // dev tool (v2e_emu_debug_timeline)
     int n_cu = 256;
-    double prof_ms[4] = {0, 0, 0, 0}; // count, rank, scan, emit (use_graph == 2)
+    double prof_ms[4] = {0, 0, 0, 0}; // count, rank, scan, emit (V2E_RUN_PROFILE)
     int prof_launches = 0;
     std::vector<float> prof_chain_us; // the chain launches of the last instrumented run, one by one
     int prof_emit_batches = 0, prof_step_launches = 0;
-    unsigned long long *run_off = nullptr; // [run_off_cap][n_clips] event offset at the start of every emission batch of the run
     int run_off_cap = 0;
     hipStream_t side = nullptr;        // the event writer of the chain: k_cemit
     std::vector<hipEvent_t> ev_fork, ev_join;
     // K-frames-per-launch chain (emu_chain.h); allocated on first use by v2e_emu_run
     int ch_ring_pref = 0; // ring depth in batches, chosen by the handle's first device-resident run (chain_ring_batches)
     int ch_K = 0, ch_D = 0, ch_nD = 3, ch_nwp = 0, ch_launch_cap = 0, ch_max_blocks = 0, ch_fused = -1, ch_inst = -1;
-    uint32_t *ch_cnt = nullptr;     // [ch_D][n_clips][npx_pad]
-    uint32_t *ch_ruleM = nullptr;   // [ch_D][n_clips]
-    uint16_t *ch_wmax = nullptr;    // [2][ch_E][n_clips][ch_nwp]
-    uint16_t *ch_wtot = nullptr;    // [3][ch_E][n_clips][nkeys_cap][ch_nwp]
-    float *ch_tsold = nullptr;      // [ch_D][n_clips][npx_pad] (refractory runs)
     void *ch_ck = nullptr;          // refractory runs: 2 launch parities x (K / 8 - 1) checkpoints x (base 8 B, lp 8 B, ts 4 B) planes
-    uint4 *ch_rec = nullptr;        // [ch_D][n_clips][npx_pad] k_ahead's per-(frame, pixel) records
     hipStream_t ahead = nullptr;    // k_ahead runs beside the chain and the emission
     std::vector<hipStream_t> spare_streams; // candidates the queue probe did not give a role (destroyed with the handle)
     hipStream_t probed_for = nullptr;       // the caller's stream the pipelined roles were last probed against
@@ -890,68 +917,38 @@ struct v2e_emu {
     std::vector<hipEvent_t> ev_ahead, ev_chain, ev_tab;
     int ch_E = 0;                   // frames per k_ahead launch / emission batch (a multiple of ch_K)
     int last_kind = -1, last_fpl = 0, last_fpb = 0; // v2e_emu_last_pipeline
-    uint32_t *ch_gM = nullptr;      // [ch_launch_cap][ch_K + 1][n_clips][ch_K]
-    unsigned *ch_bar = nullptr;     // [ch_launch_cap][2 ch_K][n_clips]: one counter per rendezvous of a launch (passes + lock-step frames)
     void *ch_base2 = nullptr, *ch_lp2 = nullptr; // second set of state planes (ping-pong between launches)
     float *ch_ts2 = nullptr;
-    CFrame *ch_cf = nullptr;        // [2][ch_E][n_clips]
-    unsigned *ch_cdone = nullptr;   // [2][ch_E][n_clips] k_cframe's per-frame completion counters
-    uint32_t *ch_cT = nullptr, *ch_ckbase = nullptr, *ch_cperm = nullptr, *ch_cpre = nullptr;
     int ch_long_batches = -1;      // large grids: 64-frame emission batches (1) or max(K, 8) (0: the ring would not fit); -1: not decided yet
-    uint32_t *ch_cpre16 = nullptr; // every 16th entry of ch_cpre (CEmitArgs::cpre16)
-    uint32_t *ch_cmask = nullptr; // the pull's per-(group, key) pixel ballots (CEmitArgs::cmask), three sets like the other tables
     int ch_nkeys_cap = 0;           // nkeys_cap the chain scratch was sized for
     int ch_pull = 0;                // the event writer of this configuration: k_cpull (1) or k_cemit
-    // ---- two scratch sets for OVERLAPPED runs (v2e_emu_run, use_graph | 1024): everything a run's head (uploads, zero fills, first
-    // records), its chain and its last emission batches touch while the run before / after it is still in flight exists twice; the
-    // fields above / below name the CURRENT set, `alt` holds the other one, swap_scratch() exchanges them before a run is enqueued.
-    // (Not doubled: the pixel state and its ping-pong set, the checkpoints: only the chain touches them, and chains never overlap.)
-    static constexpr int NPF = 21;
-    void *alt[NPF] = {};
-    void **pf(int i)
-    {
-        void **t[NPF] = {(void **)&run_ctl, (void **)&run_fidx, (void **)&run_frames, (void **)&stamp_slot, (void **)&run_off,
-                         (void **)&ch_gM, (void **)&ch_bar, (void **)&ch_rec, (void **)&ch_cnt, (void **)&ch_ruleM, (void **)&ch_tsold,
-                         (void **)&ch_wmax, (void **)&ch_wtot, (void **)&ch_cf, (void **)&ch_cdone, (void **)&ch_cT, (void **)&ch_ckbase,
-                         (void **)&ch_cperm, (void **)&ch_cpre, (void **)&ch_cmask, (void **)&ch_cpre16};
-        return t[i];
-    }
-    void *&alt_of(void **field)
-    {
-        for (int i = 0; i < NPF; ++i) if (pf(i) == field) return alt[i];
-        static void *none = nullptr;
-        return none;
-    }
+    // the two scratch sets of pipelined runs: a pipelined run flips scratch_par and takes the other set than the run before it; every
+    // other run uses the current one.  A set's buffers are allocated while it is current, when a run first needs them.
+    RunScratch sets[2];
     int scratch_par = 0;
-    void swap_scratch()
-    {
-        for (int i = 0; i < NPF; ++i) std::swap(*pf(i), alt[i]);
-        scratch_par ^= 1;
-    }
-    // what is sized by the chain configuration (K, E, keys), in both sets
+    RunScratch &cur() { return sets[scratch_par]; }
+    const RunScratch &cur() const { return sets[scratch_par]; }
+    // what the chain configuration sizes, in both sets
     void free_chain_scratch()
     {
-        for (int i = 5; i < NPF; ++i) { // from ch_gM on (run_ctl / run_fidx / run_frames / stamp_slot / run_off have their own sizes)
-            hipFree(*pf(i)); hipFree(alt[i]);
-            *pf(i) = nullptr; alt[i] = nullptr;
-        }
+        sets[0].free_chain(); sets[1].free_chain();
         hipFree(ch_ck); ch_ck = nullptr;
     }
-    // overlapped runs in flight: events of the pieces
+    // pipelined runs in flight: events of the pieces
     hipEvent_t ev_main_done2[2] = {nullptr, nullptr}, ev_tail_done2[2] = {nullptr, nullptr};
     bool piece_pending[2] = {false, false}; // set `par` has a run whose pieces may still be executing
-    const void *last_events = nullptr, *last_recs = nullptr; // buffers of the overlapped run enqueued last
+    const void *last_events = nullptr, *last_recs = nullptr; // buffers of the pipelined run enqueued last
     hipEvent_t ev_user = nullptr;
     void *recs_host[2] = {nullptr, nullptr}; // pinned: the records of the last pipelined run per scratch set (v2e_emu_run_recs)
     size_t recs_host_cap[2] = {0, 0}, recs_host_n[2] = {0, 0};
     int last_ticket = -1; // the scratch set of the run enqueued last if it went out in pieces, else -1 (v2e_emu_run_ticket)
-    // every piece of every overlapped run has completed (host-blocking; before scratch is freed or re-sized)
+    // every piece of every pipelined run has completed (host-blocking; before scratch is freed or re-sized)
     void sync_runs()
     {
         for (int q = 0; q < 2; ++q)
             if (piece_pending[q]) { if (ev_tail_done2[q]) hipEventSynchronize(ev_tail_done2[q]); if (ev_main_done2[q]) hipEventSynchronize(ev_main_done2[q]); piece_pending[q] = false; }
     }
-    // `s` waits for every piece of every overlapped run enqueued so far (no host block)
+    // `s` waits for every piece of every pipelined run enqueued so far (no host block)
     int join_runs(hipStream_t s)
     {
         for (int q = 0; q < 2; ++q)
@@ -1098,19 +1095,16 @@ int v2e_emu_create(int H, int W, int n_clips, int max_iters, int device, v2e_emu
     V2E_HIP(hipMalloc(&h->off_zero, sizeof(unsigned long long) * n_clips));
     V2E_HIP(hipMemset(h->off_zero, 0, sizeof(unsigned long long) * n_clips));
     V2E_HIP(hipHostMalloc(&h->off_host, sizeof(unsigned long long) * n_clips));
-    V2E_HIP(hipMalloc(&h->run_fidx, sizeof(uint32_t)));
     V2E_HIP(hipHostMalloc(&h->run_fidx_host, 2 * sizeof(uint32_t)));
-    V2E_HIP(hipMalloc(&h->run_frames, sizeof(void *)));
     V2E_HIP(hipHostMalloc(&h->run_frames_host, 2 * sizeof(void *)));
-    V2E_HIP(hipMalloc(&h->stamp_slot, sizeof(void *)));
-    V2E_HIP(hipMemset(h->stamp_slot, 0, sizeof(void *)));
     V2E_HIP(hipHostMalloc(&h->stamp_slot_host, 2 * sizeof(void *)));
     h->stamp_slot_host[0] = h->stamp_slot_host[1] = nullptr;
-    // the second scratch set's copies of the run's device variables (overlapped runs)
-    V2E_HIP(hipMalloc(&h->alt_of((void **)&h->run_fidx), sizeof(uint32_t)));
-    V2E_HIP(hipMalloc(&h->alt_of((void **)&h->run_frames), sizeof(void *)));
-    V2E_HIP(hipMalloc(&h->alt_of((void **)&h->stamp_slot), sizeof(void *)));
-    V2E_HIP(hipMemset(h->alt_of((void **)&h->stamp_slot), 0, sizeof(void *)));
+    for (RunScratch &r : h->sets) { // the run's device variables, in both scratch sets
+        V2E_HIP(hipMalloc(&r.run_fidx, sizeof(uint32_t)));
+        V2E_HIP(hipMalloc(&r.run_frames, sizeof(void *)));
+        V2E_HIP(hipMalloc(&r.stamp_slot, sizeof(void *)));
+        V2E_HIP(hipMemset(r.stamp_slot, 0, sizeof(void *)));
+    }
     V2E_HIP(hipDeviceSynchronize()); // the fills above are ordered on the default stream only; the caller's stream may be any
     *out = h;
     return 0;
@@ -1123,7 +1117,7 @@ int v2e_emu_destroy(v2e_emu *h)
     h->sync_runs();
     hipDeviceSynchronize();
     h->drop_graphs();
-    for (int i = 0; i < v2e_emu::NPF; ++i) hipFree(h->alt[i]);
+    for (RunScratch &r : h->sets) r.free_all();
     if (h->ev_user) hipEventDestroy(h->ev_user);
     for (int q = 0; q < 2; ++q) if (h->recs_host[q]) hipHostFree(h->recs_host[q]);
     for (int q = 0; q < 2; ++q) {
@@ -1132,12 +1126,11 @@ int v2e_emu_destroy(v2e_emu *h)
     }
 
     hipFree(h->cnt); hipFree(h->hist); hipFree(h->tot); hipFree(h->rec_ring); hipFree(h->ctl_ring);
-    hipFree(h->lut_L); hipFree(h->lut_I); hipFree(h->run_off);
+    hipFree(h->lut_L); hipFree(h->lut_I);
     for (hipEvent_t e : h->ev_fork) hipEventDestroy(e);
     for (hipEvent_t e : h->ev_join) hipEventDestroy(e);
     if (h->side) hipStreamDestroy(h->side);
-    hipFree(h->ch_cnt); hipFree(h->ch_ruleM); hipFree(h->ch_wmax); hipFree(h->ch_wtot); hipFree(h->ch_tsold); hipFree(h->ch_ck);
-    hipFree(h->ch_gM); hipFree(h->ch_bar); hipFree(h->ch_rec); hipFree(h->csr_slots);
+    hipFree(h->ch_ck); hipFree(h->csr_slots);
     for (hipEvent_t e : h->ev_ahead) hipEventDestroy(e);
     for (hipEvent_t e : h->ev_chain) hipEventDestroy(e);
     for (hipEvent_t e : h->ev_tab) hipEventDestroy(e);
@@ -1145,18 +1138,14 @@ int v2e_emu_destroy(v2e_emu *h)
     if (h->ahead) hipStreamDestroy(h->ahead);
     if (h->tabs) hipStreamDestroy(h->tabs);
     if (h->side2) hipStreamDestroy(h->side2);
-    hipFree(h->ch_base2); hipFree(h->ch_lp2); hipFree(h->ch_ts2); hipFree(h->ch_cf); hipFree(h->ch_cT); hipFree(h->ch_ckbase);
-    hipFree(h->ch_cperm); hipFree(h->ch_cpre); hipFree(h->ch_cdone); hipFree(h->ch_cmask); hipFree(h->ch_cpre16);
+    hipFree(h->ch_base2); hipFree(h->ch_lp2); hipFree(h->ch_ts2);
     if (h->ctl_host) hipHostFree(h->ctl_host);
     hipFree(h->off_dev);
     if (h->off_host) hipHostFree(h->off_host);
-    if (h->run_ctl) hipFree(h->run_ctl);
     for (int q = 0; q < 2; ++q) { if (h->run_ctl_host2[q]) hipHostFree(h->run_ctl_host2[q]); if (h->ev_stage[q]) hipEventDestroy(h->ev_stage[q]); }
-    hipFree(h->run_fidx);
     if (h->run_fidx_host) hipHostFree(h->run_fidx_host);
-    hipFree(h->run_frames);
     if (h->run_frames_host) hipHostFree(h->run_frames_host);
-    hipFree(h->stamp_slot); hipFree(h->stamps);
+    hipFree(h->stamps);
     if (h->stamp_slot_host) hipHostFree(h->stamp_slot_host);
     hipFree(h->fr_dev); hipFree(h->off_zero);
     if (h->fr_stage) hipHostFree(h->fr_stage);
@@ -1646,12 +1635,13 @@ static int enqueue_run(v2e_emu *h, const v2e_emu_params *p, const KArgs &a, cons
                        float *events, uint64_t cap, v2e_frame_rec *recs, hipStream_t s, hipEvent_t *evs = nullptr)
 {
 #define V2E_MARK(i) do { if (evs) V2E_HIP(hipEventRecord(evs[(i)], s)); } while (0)
+    const RunScratch &r = h->cur();
     const size_t esz = dtype == V2E_DT_U8 ? 1 : (dtype == V2E_DT_F32 ? 4 : 8);
     V2E_HIP(zero_async(recs, sizeof(v2e_frame_rec) * (size_t)n_frames * h->n_clips, s));
     dim3 gridw(v2e_cdiv((int64_t)h->nwaves * WAVE, BLOCK), h->n_clips);
     for (int f = 0; f < n_frames; ++f) {
         const void *fr = (const char *)frames + (size_t)f * h->n_clips * h->npx * esz;
-        const FrameCtl *ctl = h->run_ctl + (size_t)f * h->n_clips;
+        const FrameCtl *ctl = r.run_ctl + (size_t)f * h->n_clips;
         v2e_frame_rec *rec = recs + (size_t)f * h->n_clips;
         const v2e_frame_rec *rec_prev = f > 0 ? rec - h->n_clips : nullptr;
         V2E_MARK(4 * f + 0);
@@ -1665,15 +1655,15 @@ static int enqueue_run(v2e_emu *h, const v2e_emu_params *p, const KArgs &a, cons
                                               h->csr_ap[f], h->csr_ah[f], h->csr_steps[f], h->csr_thr, h->csr_slots, h->csr_steps_dev + f, s);
             if (rcs) return rcs;
         }
-        int rc = launch_count(h, a, p->f64_state, fr, dtype, ctl, h->run_fidx, (uint32_t)f, nullptr, nullptr, rec, s);
+        int rc = launch_count(h, a, p->f64_state, fr, dtype, ctl, r.run_fidx, (uint32_t)f, nullptr, nullptr, rec, s);
         if (rc) return rc;
         V2E_MARK(4 * f + 1);
         k_rank<<<gridw, BLOCK, 0, s>>>(a, ctl, rec, nullptr, 0);
         V2E_MARK(4 * f + 2);
         k_scan<<<dim3(SCAN_BLOCKS, h->n_clips), BLOCK, 0, s>>>(a, rec);
         V2E_MARK(4 * f + 3);
-        if (p->f64_state) k_emit<double><<<gridw, BLOCK, 0, s>>>(a, ctl, rec, rec_prev, nullptr, h->run_fidx, (uint32_t)f, nullptr, 0, (float4 *)events, cap);
-        else k_emit<float><<<gridw, BLOCK, 0, s>>>(a, ctl, rec, rec_prev, nullptr, h->run_fidx, (uint32_t)f, nullptr, 0, (float4 *)events, cap);
+        if (p->f64_state) k_emit<double><<<gridw, BLOCK, 0, s>>>(a, ctl, rec, rec_prev, nullptr, r.run_fidx, (uint32_t)f, nullptr, 0, (float4 *)events, cap);
+        else k_emit<float><<<gridw, BLOCK, 0, s>>>(a, ctl, rec, rec_prev, nullptr, r.run_fidx, (uint32_t)f, nullptr, 0, (float4 *)events, cap);
     }
     V2E_MARK(4 * n_frames);
 #undef V2E_MARK
@@ -1683,21 +1673,16 @@ static int enqueue_run(v2e_emu *h, const v2e_emu_params *p, const KArgs &a, cons
 
 
 // ------------------------------------------------------------------ launch scheduling of the chain pipeline
-// The run is a DAG over three logical streams (chain, k_ahead + emission tables, event writer) with cross edges between
-// all of them.  It is either enqueued on three HIP streams with events, or built as an explicit hipGraph (kernel nodes
-// with their dependency lists).  Stream capture is NOT used for it: hipStreamEndCapture of a capture with edges between
-// two forked streams segfaults on this runtime (ROCm 7.0 / HIP 7.0.5; round 2 had met the same with a fourth stream).
+// The run is a DAG over logical streams (chain, k_ahead, emission tables, event rows) with cross edges between them, enqueued on
+// HIP streams with events -- under stream capture for a graph run (edges between the origin stream and a forked stream only:
+// hipStreamEndCapture of a capture with edges between two forked streams segfaults on this runtime, ROCm 7.0 / HIP 7.0.5).
 enum { ST_MAIN = 0, ST_AHEAD = 1, ST_SIDE = 2, ST_TAB = 3, ST_SIDE2 = 4, ST_COUNT = 5 };
-enum { EV_FORK = 0, EV_JOIN = 1, EV_AHEAD = 2, EV_CHAIN = 3, EV_TAB = 4, EV_KINDS = 5 };
+enum { EV_FORK = 0, EV_JOIN = 1, EV_AHEAD = 2, EV_CHAIN = 3, EV_TAB = 4 };
 
-// dev tool (scripts/step_stamps.py): sequence-numbered device time stamps from inside a run's graph: buf[0] counts, buf[1 + i] = time
+// a logical stream -> its HIP stream; an (event kind, index) -> the handle's HIP event
 struct Sched {
     v2e_emu *h;
     hipStream_t st[ST_COUNT];
-    hipGraph_t graph = nullptr; // non-null: build nodes instead of launching
-    std::vector<hipGraphNode_t> pos[ST_COUNT];                  // what the next node of a logical stream depends on
-    std::vector<std::vector<hipGraphNode_t>> evdeps;     // graph mode: the dependencies an event stands for
-    int ev_cap = 0;
 
     hipEvent_t real_event(int kind, int idx) const
     {
@@ -1709,37 +1694,10 @@ struct Sched {
         default: return h->ev_tab[idx];
         }
     }
-    static void merge(std::vector<hipGraphNode_t> &dst, const std::vector<hipGraphNode_t> &src)
-    {
-        for (hipGraphNode_t n : src) {
-            bool dup = false;
-            for (hipGraphNode_t d : dst) dup = dup || d == n;
-            if (!dup) dst.push_back(n);
-        }
-    }
     int kernel(int s, const void *fn, dim3 grid, dim3 block, size_t lds, void **args)
     {
-        if (!graph) {
-            V2E_HIP(hipLaunchKernel(fn, grid, block, args, lds, st[s]));
-            return 0;
-        }
-        hipKernelNodeParams kp;
-        memset(&kp, 0, sizeof(kp));
-        kp.func = const_cast<void *>(fn);
-        kp.gridDim = grid; kp.blockDim = block; kp.sharedMemBytes = (unsigned)lds;
-        kp.kernelParams = args; kp.extra = nullptr;
-        hipGraphNode_t node;
-        V2E_HIP(hipGraphAddKernelNode(&node, graph, pos[s].empty() ? nullptr : pos[s].data(), pos[s].size(), &kp));
-        pos[s].assign(1, node);
+        V2E_HIP(hipLaunchKernel(fn, grid, block, args, lds, st[s]));
         return 0;
-    }
-    int zero(int s, void *ptr, size_t bytes)
-    {
-        size_t n = (bytes + 3) / 4;
-        if (n == 0) return 0;
-        uint32_t *p32 = (uint32_t *)ptr;
-        void *args[] = {(void *)&p32, (void *)&n};
-        return kernel(s, (const void *)k_zero_words, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, args);
     }
     int zero4(int s, void *const ptr[4], const size_t bytes[4])
     {
@@ -1752,14 +1710,12 @@ struct Sched {
     }
     int record(int kind, int idx, int s)
     {
-        if (!graph) { V2E_HIP(hipEventRecord(real_event(kind, idx), st[s])); return 0; }
-        evdeps[(size_t)kind * ev_cap + idx] = pos[s];
+        V2E_HIP(hipEventRecord(real_event(kind, idx), st[s]));
         return 0;
     }
     int wait(int s, int kind, int idx)
     {
-        if (!graph) { V2E_HIP(hipStreamWaitEvent(st[s], real_event(kind, idx), 0)); return 0; }
-        merge(pos[s], evdeps[(size_t)kind * ev_cap + idx]);
+        V2E_HIP(hipStreamWaitEvent(st[s], real_event(kind, idx), 0));
         return 0;
     }
 };
@@ -1774,10 +1730,9 @@ static bool chain_small_grid(const v2e_emu *h) { return (long long)h->ngroups * 
 // and 1280x720 do not care (14.5-14.6 / 11.9-12.1 Gev/s either way) -- but PIPELINED runs of a small grid, whose k_ahead runs a whole
 // run ahead and whose event rows have a stream of their own, gain from never waiting inside a 300-frame run: ring 3 681-685 us per
 // step, 4 668-671, 5 662-664, 6 657-673, 8 671 (profiles/r06_emulator_experiments.txt item 21).  A handle keeps the depth its FIRST
-// device-resident run chose (no re-allocation when a caller mixes modes); V2E_AMD_CHAIN_RING overrides.
+// device-resident run chose (no re-allocation when a caller mixes modes).
 static int chain_ring_batches(v2e_emu *h, bool pipelined)
 {
-    if (const char *ev = getenv("V2E_AMD_CHAIN_RING")) { const int v = atoi(ev); if (v >= 3 && v <= 16) return v; }
     if (h->ch_ring_pref == 0) h->ch_ring_pref = (pipelined && chain_small_grid(h) && h->n_clips == 1) ? 5 : 3;
     return h->ch_ring_pref;
 }
@@ -1831,15 +1786,15 @@ static int chain_blocks_per_cu(v2e_emu *h, bool f64, int dtype, bool fused, bool
 // ~1 % of the frames of the benchmark clip) repeats a launch from a checkpoint.  Small grids (bounded by latency) and large
 // grids without a refractory period: 32 (1280x720 noisy: 16 frames 6.24, 32 frames 6.49 Gev/s); large grids where a redo is
 // possible: 8.  A clip whose workgroups cannot all be resident cannot hold the redo rendezvous: one frame per launch, where
-// the one frame a redo fixes is the launch's last and nothing is left to verify (|128 asks for that too: clips on which the
-// rule is active on most frames would redo most launches).
-static int chain_frames_per_launch(const v2e_emu *h, bool has_refr, int use_graph, int max_blocks)
+// the one frame a redo fixes is the launch's last and nothing is left to verify (V2E_RUN_ONE_FRAME_PER_LAUNCH asks for that too:
+// clips on which the rule is active on most frames would redo most launches).
+static int chain_frames_per_launch(const v2e_emu *h, bool has_refr, int flags, int max_blocks)
 {
     // (without a refractory period nothing is speculated and nothing redone: the longest launch the kernel supports -- 1280x720 noisy,
     //  pipelined, round 6: 64 frames 13.6-14.1 Gev/s, 32 13.0-13.5, 16 12.6-13.0)
     int K = !has_refr ? CHAIN_K_MAX : (chain_small_grid(h) ? 32 : 8);
     if (const char *ev = getenv("V2E_AMD_CHAIN_K")) { const int v = atoi(ev); if (v >= 1 && v <= CHAIN_K_MAX) K = v; }
-    if (has_refr && ((use_graph & 128) || h->ngroups > max_blocks)) K = 1;
+    if (has_refr && ((flags & V2E_RUN_ONE_FRAME_PER_LAUNCH) || h->ngroups > max_blocks)) K = 1;
     return K;
 }
 
@@ -1890,15 +1845,15 @@ static bool emit_pull(size_t table_bytes)
     return table_bytes <= free_b / 4 && table_bytes <= budget;
 }
 
-static int chain_alloc(v2e_emu *h, const v2e_emu_params *p, int dtype, int n_frames, int use_graph)
+static int chain_alloc(v2e_emu *h, const v2e_emu_params *p, int dtype, int n_frames, int flags, bool pipelined)
 {
     const bool has_refr = p->refractory_period_s > 0;
-    const int nD = chain_ring_batches(h, (use_graph & 1024) != 0 && (use_graph & 3) == 0);
+    const int nD = chain_ring_batches(h, pipelined);
     const bool fused = chain_fused_records(h, dtype, nD);
     const int inst = (p->f64_state ? 1 : 0) | ((dtype & 3) << 1) | (fused ? 8 : 0);
     const bool allon_p = p->cutoff_hz > 0 && p->leak_rate_hz > 0 && p->shot_noise_rate_hz > 0 && has_refr;
     const int max_blocks = chain_blocks_per_cu(h, p->f64_state != 0, dtype, fused, allon_p) * h->n_cu;
-    const int K = chain_frames_per_launch(h, has_refr, use_graph, max_blocks);
+    const int K = chain_frames_per_launch(h, has_refr, flags, max_blocks);
     // frames per k_ahead launch and per emission batch: a multiple of K, 64 frames (the emission kernels are bound by per-wave latency
     // and by the launch gaps between them, and this runtime runs the captured graph's chain and emission kernels one after the
     // other: fewer, larger batches -- 346x260, round 3: 64 frames 8.7 Gev/s, 32 frames 7.7; 1280x720 noisy, round 5 with the pull
@@ -1920,8 +1875,8 @@ static int chain_alloc(v2e_emu *h, const v2e_emu_params *p, int dtype, int n_fra
     m = std::max(1, std::min(m, 64 / K)); // k_cemit sums a batch's per-frame event counts one frame per lane
     const int E = m * K;
     if (h->ch_K != K || h->ch_E != E || h->ch_nkeys_cap != h->nkeys_cap || h->ch_fused != (int)fused || h->ch_nD != nD) {
-        // a new configuration: everything sized by it goes, in BOTH scratch sets (overlapped runs alternate between two, see
-        // v2e_emu::swap_scratch); what the run needs is allocated below, for the set that is current
+        // a new configuration: everything sized by it goes, in BOTH scratch sets; what the run needs is allocated below, for the set
+        // that is current
         h->sync_runs();
         h->free_chain_scratch();
         h->ch_launch_cap = 0;
@@ -1941,30 +1896,31 @@ static int chain_alloc(v2e_emu *h, const v2e_emu_params *p, int dtype, int n_fra
         h->drop_graphs();
     }
     const size_t nc = (size_t)h->n_clips;
-    if (!h->ch_cnt) {
-        V2E_HIP(hipMalloc(&h->ch_cnt, sizeof(uint32_t) * h->ch_D * nc * h->npx_pad));
-        V2E_HIP(hipMalloc(&h->ch_ruleM, sizeof(uint32_t) * h->ch_D * nc));
-        V2E_HIP(hipMemset(h->ch_ruleM, 0, sizeof(uint32_t) * h->ch_D * nc));
+    RunScratch &r = h->cur();
+    if (!r.ch_cnt) {
+        V2E_HIP(hipMalloc(&r.ch_cnt, sizeof(uint32_t) * h->ch_D * nc * h->npx_pad));
+        V2E_HIP(hipMalloc(&r.ch_ruleM, sizeof(uint32_t) * h->ch_D * nc));
+        V2E_HIP(hipMemset(r.ch_ruleM, 0, sizeof(uint32_t) * h->ch_D * nc));
         // three sets of emission tables in rotation: the tables of batches b + 1, b + 2 are built while k_cemit(b) reads its own
-        V2E_HIP(hipMalloc(&h->ch_wmax, 3 * sizeof(uint16_t) * E * nc * h->ch_nwp));
-        V2E_HIP(hipMemset(h->ch_wmax, 0, 3 * sizeof(uint16_t) * E * nc * h->ch_nwp));
-        V2E_HIP(hipMalloc(&h->ch_wtot, sizeof(uint16_t) * 3 * E * nc * h->nkeys_cap * h->ch_nwp));
-        V2E_HIP(hipMemset(h->ch_wtot, 0, sizeof(uint16_t) * 3 * E * nc * h->nkeys_cap * h->ch_nwp));
-        V2E_HIP(hipMalloc(&h->ch_cf, 3 * sizeof(CFrame) * E * nc));
-        V2E_HIP(hipMemset(h->ch_cf, 0, 3 * sizeof(CFrame) * E * nc));
-        V2E_HIP(hipMalloc(&h->ch_cdone, 3 * sizeof(unsigned) * E * nc));
-        V2E_HIP(hipMemset(h->ch_cdone, 0, 3 * sizeof(unsigned) * E * nc));
-        V2E_HIP(hipMalloc(&h->ch_cT, 3 * sizeof(uint32_t) * E * nc * h->nkeys_cap));
-        V2E_HIP(hipMalloc(&h->ch_ckbase, 3 * sizeof(uint32_t) * E * nc * h->nkeys_cap));
-        V2E_HIP(hipMalloc(&h->ch_cperm, 3 * sizeof(uint32_t) * E * nc * h->max_iters * 8));
-        V2E_HIP(hipMalloc(&h->ch_cpre, 3 * sizeof(uint32_t) * E * nc * h->nkeys_cap * h->ch_nwp));
+        V2E_HIP(hipMalloc(&r.ch_wmax, 3 * sizeof(uint16_t) * E * nc * h->ch_nwp));
+        V2E_HIP(hipMemset(r.ch_wmax, 0, 3 * sizeof(uint16_t) * E * nc * h->ch_nwp));
+        V2E_HIP(hipMalloc(&r.ch_wtot, sizeof(uint16_t) * 3 * E * nc * h->nkeys_cap * h->ch_nwp));
+        V2E_HIP(hipMemset(r.ch_wtot, 0, sizeof(uint16_t) * 3 * E * nc * h->nkeys_cap * h->ch_nwp));
+        V2E_HIP(hipMalloc(&r.ch_cf, 3 * sizeof(CFrame) * E * nc));
+        V2E_HIP(hipMemset(r.ch_cf, 0, 3 * sizeof(CFrame) * E * nc));
+        V2E_HIP(hipMalloc(&r.ch_cdone, 3 * sizeof(unsigned) * E * nc));
+        V2E_HIP(hipMemset(r.ch_cdone, 0, 3 * sizeof(unsigned) * E * nc));
+        V2E_HIP(hipMalloc(&r.ch_cT, 3 * sizeof(uint32_t) * E * nc * h->nkeys_cap));
+        V2E_HIP(hipMalloc(&r.ch_ckbase, 3 * sizeof(uint32_t) * E * nc * h->nkeys_cap));
+        V2E_HIP(hipMalloc(&r.ch_cperm, 3 * sizeof(uint32_t) * E * nc * h->max_iters * 8));
+        V2E_HIP(hipMalloc(&r.ch_cpre, 3 * sizeof(uint32_t) * E * nc * h->nkeys_cap * h->ch_nwp));
         if (h->ch_pull) {
-            V2E_HIP(hipMalloc(&h->ch_cmask, 3 * sizeof(uint32_t) * 2 * GPX * E * nc * h->nkeys_cap * h->ch_nwp));
-            V2E_HIP(hipMalloc(&h->ch_cpre16, 3 * sizeof(uint32_t) * E * nc * h->nkeys_cap * (h->ch_nwp / 16)));
+            V2E_HIP(hipMalloc(&r.ch_cmask, 3 * sizeof(uint32_t) * 2 * GPX * E * nc * h->nkeys_cap * h->ch_nwp));
+            V2E_HIP(hipMalloc(&r.ch_cpre16, 3 * sizeof(uint32_t) * E * nc * h->nkeys_cap * (h->ch_nwp / 16)));
         }
         if (!fused) { // (zero once: k_ahead never writes a slot's padding [npx, npx_pad), and k_chain's lanes beyond the frame read it)
-            V2E_HIP(hipMalloc(&h->ch_rec, sizeof(uint4) * (size_t)h->ch_D * nc * h->npx_pad));
-            V2E_HIP(hipMemset(h->ch_rec, 0, sizeof(uint4) * (size_t)h->ch_D * nc * h->npx_pad));
+            V2E_HIP(hipMalloc(&r.ch_rec, sizeof(uint4) * (size_t)h->ch_D * nc * h->npx_pad));
+            V2E_HIP(hipMemset(r.ch_rec, 0, sizeof(uint4) * (size_t)h->ch_D * nc * h->npx_pad));
         }
         // The fills above are ordered on the DEFAULT stream only, and a pipelined run's head (its k_ahead records, its tables) goes out on
         // streams of the handle that do not wait for it: enqueued behind a run still executing on the default stream, the record ring's
@@ -1978,12 +1934,11 @@ static int chain_alloc(v2e_emu *h, const v2e_emu_params *p, int dtype, int n_fra
     const int n_launch = (n_frames + K - 1) / K + 1;
     if (n_launch + 2 > h->run_off_cap) {
         h->sync_runs();
-        hipFree(h->run_off); hipFree(h->alt_of((void **)&h->run_off));
-        h->run_off = nullptr; h->alt_of((void **)&h->run_off) = nullptr;
+        for (RunScratch &q : h->sets) { hipFree(q.run_off); q.run_off = nullptr; }
         h->run_off_cap = n_launch + 2;
         h->drop_graphs();
     }
-    if (!h->run_off) V2E_HIP(hipMalloc(&h->run_off, sizeof(unsigned long long) * (size_t)h->run_off_cap * h->n_clips));
+    if (!r.run_off) V2E_HIP(hipMalloc(&r.run_off, sizeof(unsigned long long) * (size_t)h->run_off_cap * h->n_clips));
     if (!h->ahead) V2E_HIP(hipStreamCreateWithFlags(&h->ahead, hipStreamNonBlocking));
     if (!h->tabs) V2E_HIP(hipStreamCreateWithFlags(&h->tabs, hipStreamNonBlocking));
     if (!h->side2) V2E_HIP(hipStreamCreateWithFlags(&h->side2, hipStreamNonBlocking));
@@ -1998,7 +1953,7 @@ static int chain_alloc(v2e_emu *h, const v2e_emu_params *p, int dtype, int n_fra
     if (grow(h->ev_ahead, n_launch + 1) || grow(h->ev_chain, n_launch + 1) || grow(h->ev_fork, n_launch + 1) ||
         grow(h->ev_join, n_launch + 1) || grow(h->ev_tab, n_launch + 1)) return V2E_EHIP;
     if (has_refr) {
-        if (!h->ch_tsold) V2E_HIP(hipMalloc(&h->ch_tsold, sizeof(float) * (size_t)h->ch_D * h->n_clips * h->npx_pad));
+        if (!r.ch_tsold) V2E_HIP(hipMalloc(&r.ch_tsold, sizeof(float) * (size_t)h->ch_D * h->n_clips * h->npx_pad));
         if (!h->ch_ck && K > CHAIN_SUB) V2E_HIP(hipMalloc(&h->ch_ck, (size_t)2 * (K / CHAIN_SUB - 1 + (K % CHAIN_SUB ? 1 : 0)) * 20 * h->n_clips * h->npx_pad)); // see ChainArgs::ckc_base
         if (!h->ch_base2) {
             const size_t n = (size_t)h->n_clips * h->npx_pad;
@@ -2012,14 +1967,13 @@ static int chain_alloc(v2e_emu *h, const v2e_emu_params *p, int dtype, int n_fra
         }
         if (n_launch > h->ch_launch_cap) {
             h->sync_runs();
-            hipFree(h->ch_gM); hipFree(h->ch_bar); hipFree(h->alt_of((void **)&h->ch_gM)); hipFree(h->alt_of((void **)&h->ch_bar));
-            h->ch_gM = nullptr; h->ch_bar = nullptr; h->alt_of((void **)&h->ch_gM) = nullptr; h->alt_of((void **)&h->ch_bar) = nullptr;
+            for (RunScratch &q : h->sets) { hipFree(q.ch_gM); hipFree(q.ch_bar); q.ch_gM = nullptr; q.ch_bar = nullptr; }
             h->ch_launch_cap = n_launch;
             h->drop_graphs();
         }
-        if (!h->ch_gM) {
-            V2E_HIP(hipMalloc(&h->ch_gM, sizeof(uint32_t) * (size_t)h->ch_launch_cap * (K + 1) * h->n_clips * K));
-            V2E_HIP(hipMalloc(&h->ch_bar, sizeof(unsigned) * (size_t)h->ch_launch_cap * 2 * K * h->n_clips));
+        if (!r.ch_gM) {
+            V2E_HIP(hipMalloc(&r.ch_gM, sizeof(uint32_t) * (size_t)h->ch_launch_cap * (K + 1) * h->n_clips * K));
+            V2E_HIP(hipMalloc(&r.ch_bar, sizeof(unsigned) * (size_t)h->ch_launch_cap * 2 * K * h->n_clips));
             h->drop_graphs();
         }
     }
@@ -2037,10 +1991,17 @@ static bool chain_eligible(const v2e_emu *h, const v2e_emu_params *p, int dtype)
     return true;
 }
 
-static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a_in, const void *frames, int dtype, int n_frames,
-                             float *events, uint64_t cap, v2e_frame_rec *recs, hipStream_t s, hipGraph_t graph = nullptr,
-                             std::vector<hipEvent_t> *ev_main = nullptr, std::vector<hipEvent_t> *ev_side = nullptr,
-                             bool capturing = false, bool pipelined = false)
+// How enqueue_run_chain puts a run out
+enum class ChainMode {
+    plain,     // on the handle's streams, forked from and joined into the caller's stream
+    captured,  // the same under stream capture: edges between the origin stream and a forked stream only, so tables and rows share ST_SIDE
+    pipelined, // the caller's stream carries the chain only; head and emission go to the handle's streams and are not joined
+    profiled,  // as plain, but every kernel on the caller's stream, with HIP events around the chain launches and the event rows (marks)
+};
+struct ChainMarks { std::vector<hipEvent_t> chain, rows; }; // the events of a profiled run, in pairs (before, after)
+
+static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a_in, int dtype, int n_frames, float *events,
+                             uint64_t cap, v2e_frame_rec *recs, hipStream_t s, ChainMode mode, ChainMarks *marks = nullptr)
 {
     // Three logical streams: the chain (k_chain, K frames per launch); k_ahead and the emission tables (k_ctot, k_cframe);
     // the event writer k_cemit; the last two in batches of E = m K frames (batch b = frames [b E, (b + 1) E) = chain
@@ -2049,6 +2010,8 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
     //   tables(b)   once batch b is final: after the launch that validated its last K frames (or, without a refractory
     //               period, after its last launch); k_cemit(b) after tables(b) and k_cemit(b - 1) (running event offset)
     //   chain launch b m overwrites the ring slots of batch b - nD: after k_cemit(b - nD)   (nD = ch_D / E batches in the ring)
+    const bool captured = mode == ChainMode::captured, pipelined = mode == ChainMode::pipelined;
+    const RunScratch &r = h->cur();
     const size_t esz = dtype == V2E_DT_U8 ? 1 : (dtype == V2E_DT_F32 ? 4 : 8);
     const bool has_refr = p->refractory_period_s > 0;
     const int K = h->ch_K, E = h->ch_E, m = E / K, D = h->ch_D, NC = h->n_clips, nD = h->ch_nD;
@@ -2057,20 +2020,16 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
     const int nL = (int)plan.size();
     const int nB = (n_frames + K - 1) / K;
     const int nEB = (n_frames + E - 1) / E;
-    KArgs a = a_in; // kernel arguments are passed by address (hipLaunchKernel / kernel nodes copy them at the call)
+    KArgs a = a_in; // kernel arguments are passed by address (hipLaunchKernel copies them at the call)
     Sched sc;
-    sc.h = h; sc.st[ST_MAIN] = s; sc.st[ST_AHEAD] = h->ahead; sc.st[ST_SIDE] = h->side; sc.st[ST_TAB] = h->tabs; sc.st[ST_SIDE2] = h->side2; sc.graph = graph;
-    if (ev_main) // instrumented run: every kernel on the one stream, so that a launch's HIP events bracket that kernel running alone --
+    sc.h = h; sc.st[ST_MAIN] = s; sc.st[ST_AHEAD] = h->ahead; sc.st[ST_SIDE] = h->side; sc.st[ST_TAB] = h->tabs; sc.st[ST_SIDE2] = h->side2;
+    if (mode == ChainMode::profiled) // every kernel on the one stream, so that a launch's HIP events bracket that kernel running alone --
         for (int q = 0; q < ST_COUNT; ++q) sc.st[q] = s; // which is how the captured graph of the timed runs executes on this runtime
-    if (graph) {
-        sc.ev_cap = nL + 2;
-        sc.evdeps.assign((size_t)EV_KINDS * sc.ev_cap, std::vector<hipGraphNode_t>());
-    }
-    auto mark = [&](std::vector<hipEvent_t> *v, hipStream_t stq) -> int { // instrumented runs (never graphs)
-        if (!v || graph) return 0;
+    auto mark = [&](bool rows, hipStream_t stq) -> int {
+        if (mode != ChainMode::profiled) return 0;
         hipEvent_t e;
         V2E_HIP(hipEventCreate(&e));
-        v->push_back(e);
+        (rows ? marks->rows : marks->chain).push_back(e);
         V2E_HIP(hipEventRecord(e, stq));
         return 0;
     };
@@ -2079,32 +2038,12 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
     int gy = NC;
     if (has_refr && K > 1) gy = std::max(1, std::min(NC, h->ch_max_blocks / std::max(h->ngroups, 1)));
     dim3 grid(h->ngroups, gy);
-    constexpr bool no_emit = false;
-    const bool no_emit_run = false;
-    constexpr int chain_prio = 3; // wave priority of the chain (measured against 0 in round 3)
-    // occupancy cap of the kernels that run BESIDE the chain (k_ahead, k_ctot, k_cemit): dynamic LDS they do not use, so that a
-    // CU holds at most floor(160 KB / pad) of their workgroups (0: no cap)
-    constexpr int side_pad = 0; // (an LDS pad capping the side kernels' occupancy was measured in round 3 and bought nothing)
-    constexpr int bar_light = 1; // the fence-free rendezvous (round 4; the fenced one of round 3 is still in clip_barrier)
-    // lock-step frames in redo passes (emu_chain.h): measured round 4 with the fence-free rendezvous, A/B in one process each:
-    // a launch whose rule-on frames come in a run 109-112 -> 89-92 us, a launch with a single rule-on frame 54-60 -> 68-71 us
-    // (the extra rendezvous is ~10 us inside the frame loop: it also drains the record prefetch), 10.4-10.6 against 10.8-11.0
-    // Gev/s on the benchmark clip: off by default, kept behind V2E_AMD_LOCKSTEP=1 (GPU parity suite green with it on)
-    constexpr int lockstep = 0;
-    // Under stream capture only edges between the origin stream and a forked stream are safe (edges between two forked
-    // streams crash hipStreamEndCapture on this runtime): tables and rows then share the side stream.
-    constexpr int tab_env = ST_TAB; // plain streams: tables on a stream of their own
-    constexpr bool tabs_on_main = false;
-    // pipelined plain launches (v2e_emu_run, mode 0 | 1024): four streams in all
-    // -- the caller's (the chain), k_ahead's, the emission tables' (h->side) and the event rows' (h->side2): with tables and rows on one
-    // stream that stream was busy ~500 of a step's 720 us and the chain waited for it where the ring of frame slots wraps (device
-    // stamps: 57 us before the first launch of batch 3; with the rows on their own stream 19, 717-732 -> 699-713 us per step).
-    // (The tables on the k_ahead stream instead: the next run's head queues behind this run's last tables, 290 us between two runs'
-    // chains.)
-    constexpr bool pipe_rows_own = true;
-    const int tab_stream = capturing ? (tabs_on_main ? ST_MAIN : ST_SIDE) : (pipelined ? ST_SIDE : tab_env);
+    // Where the emission goes.  Captured: tables and rows on ST_SIDE (the only forked stream with edges to the origin), the rows
+    // carrying the running event offset forward themselves.  Pipelined: tables on ST_SIDE, rows on ST_SIDE2 -- with both on one stream
+    // that stream was busy ~500 of a step's 720 us and the chain waited for it where the ring wraps (717-732 -> 699-713 us per step).
+    // Plain: tables on ST_TAB, rows alternating ST_SIDE / ST_SIDE2 by batch (two batches' rows side by side, k_coff behind the tables).
+    const int tab_stream = captured || pipelined ? ST_SIDE : ST_TAB;
     constexpr int NSET = 3; // emission table sets (chain_alloc sizes them)
-    constexpr bool one_row_stream = false;
     // b: the emission's slot (event indices, table set b % NSET, event offsets run_off[b] -> run_off[b + 1]); frames [ef0, ef0 + enE).
     // A batch is normally slot b = frames [b E, (b + 1) E); the run's LAST batch may be emitted in two pieces (slots nEB - 1, nEB).
     // (Round 5 measured the tables of the run's LAST pieces on the chain's stream, beside the rows of the batch before on the side
@@ -2112,85 +2051,75 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
     auto launch_emission = [&](int b, int ef0, int enE) -> int { // EV_FORK[b] has been recorded on the chain stream
         CEmitArgs ea;
         memset(&ea, 0, sizeof(ea));
-        ea.ctl = h->run_ctl; ea.recs = recs; ea.fidx_base = h->run_fidx;
+        ea.ctl = r.run_ctl; ea.recs = recs; ea.fidx_base = r.run_fidx;
         ea.f0 = ef0; ea.nE = enE; ea.D = D; ea.n_clips = NC; ea.slot0 = ef0 % D;
         ea.nwp = h->ch_nwp; ea.nwaves = chain_egroups(h); ea.E = E; // emission groups (GROUP_PX pixels, one wave each)
-        ea.cnt = h->ch_cnt; ea.tsold = has_refr ? h->ch_tsold : nullptr; ea.ruleM = has_refr ? h->ch_ruleM : nullptr;
+        ea.cnt = r.ch_cnt; ea.tsold = has_refr ? r.ch_tsold : nullptr; ea.ruleM = has_refr ? r.ch_ruleM : nullptr;
         const size_t set = (size_t)(b % NSET) * E * NC; // table set of this batch
-        ea.wmax = h->ch_wmax + set * h->ch_nwp; ea.wtot = h->ch_wtot + set * h->nkeys_cap * h->ch_nwp;
-        ea.cf = h->ch_cf + set; ea.cT = h->ch_cT + set * h->nkeys_cap; ea.ckbase = h->ch_ckbase + set * h->nkeys_cap;
-        ea.cperm = h->ch_cperm + set * h->max_iters * 8; ea.cpre = h->ch_cpre + set * h->nkeys_cap * h->ch_nwp;
-        ea.cdone = h->ch_cdone + set;
-        const bool pull = h->ch_cmask != nullptr;
-        ea.cmask = pull ? h->ch_cmask + set * h->ch_nwp * h->nkeys_cap * 2 * GPX : nullptr;
+        ea.wmax = r.ch_wmax + set * h->ch_nwp; ea.wtot = r.ch_wtot + set * h->nkeys_cap * h->ch_nwp;
+        ea.cf = r.ch_cf + set; ea.cT = r.ch_cT + set * h->nkeys_cap; ea.ckbase = r.ch_ckbase + set * h->nkeys_cap;
+        ea.cperm = r.ch_cperm + set * h->max_iters * 8; ea.cpre = r.ch_cpre + set * h->nkeys_cap * h->ch_nwp;
+        ea.cdone = r.ch_cdone + set;
+        const bool pull = r.ch_cmask != nullptr;
+        ea.cmask = pull ? r.ch_cmask + set * h->ch_nwp * h->nkeys_cap * 2 * GPX : nullptr;
         // k_cpull: small frames search a whole prefix row in LDS (346x260: 1.4 KB per key), a workgroup per ~2048 pixels' worth of
         // a frame's rows; large ones search every 16th entry there and one line from L2, and take more, smaller workgroups (their
         // batches are few frames: the launch needs the parallelism)
         bool two = h->ch_nwp > 1024;
         if (const char *ev = getenv("V2E_AMD_PULL_TWO_LEVEL")) two = atoi(ev) != 0;
-        ea.cpre16 = pull && two ? h->ch_cpre16 + set * h->nkeys_cap * (h->ch_nwp / 16) : nullptr;
+        ea.cpre16 = pull && two ? r.ch_cpre16 + set * h->nkeys_cap * (h->ch_nwp / 16) : nullptr;
         ea.wpf = std::max(4, std::min(two ? 128 : 64, h->npx / 2048)); // (1280x720 noisy, round 5: 450 workgroups per frame 9.28, 128: 9.68, push 9.41 Gev/s)
         ea.p2 = two ? 16 : 64;
         while (ea.p2 < (two ? h->ch_nwp / 16 : ea.nwaves)) ea.p2 *= 2;
         ea.events = (float4 *)events; ea.cap = cap;
-        ea.off_in = h->run_off + (size_t)b * NC;
-        ea.off_out = h->run_off + (size_t)(b + 1) * NC;
+        ea.off_in = r.run_off + (size_t)b * NC;
+        ea.off_out = r.run_off + (size_t)(b + 1) * NC;
         // event records of k_cemit: 256 x ich per group (wave) and pass.  The chain's workgroups need their LDS (5 KB per frame)
         // on every CU: 4 iterations per pass (measured at 346x260: 3 / 6 / 10 per pass 10.47 / 10.30 / 10.31 Gev/s) keep an emission workgroup of four groups at 16 KB
-        constexpr int ich_env = 0;
-        ea.ich = (ich_env >= 1 && ich_env <= 31) ? ich_env : 4;
+        ea.ich = 4;
         ea.capw = GROUP_PX * ea.ich;
-        const bool rows_own = pipelined && pipe_rows_own;
-        // (one row stream: the rows carry the running event offset forward themselves -- no k_coff launch)
-        ea.coff_in_cemit = (tab_stream == ST_SIDE || tab_stream == ST_MAIN || one_row_stream || rows_own) ? 1 : 0;
+        ea.coff_in_cemit = captured || pipelined ? 1 : 0; // (one row stream per run: no k_coff launch)
         // frames per workgroup (measured at 346x260, 32-frame batches: k_ctot 4 frames 13 us, 32 frames 37 us; k_cemit 1 frame
         // 34 us, 8 frames 45 us -- these kernels are bound by the latency of a wave's dependent loads, not by wave dispatch:
         // more, shorter waves win)
-        constexpr int zpw_env = 0;
-        (void)zpw_env;
         ea.zpw_tot = CTOT_ZF;
         ea.zpw_emit = 1; // (k_cemit: one frame per workgroup; several per workgroup measured slower and cost 25 % more instructions)
         const int REC_LDS = (ea.capw + WAVE) * 4 * (BLOCK / WAVE);
         const int egx = (chain_egroups(h) + BLOCK / WAVE - 1) / (BLOCK / WAVE); // workgroups of four emission groups
         void *args[] = {(void *)&a, (void *)&ea};
-        // tables on a stream of their own (NSET table sets rotate: tables(b + 1) are built while k_cemit(b) reads those of b;
-        // k_cemit(b - NSET), which read this set last, is waited for), rows on the side stream
-        if (tab_stream != ST_MAIN && sc.wait(tab_stream, EV_FORK, b)) return V2E_EHIP;
-        if (b >= NSET && (tab_stream != ST_SIDE || rows_own) && sc.wait(tab_stream, EV_JOIN, b - NSET)) return V2E_EHIP;
-        if (!no_emit) {
-            if (sc.kernel(tab_stream, (const void *)k_ctot, dim3(egx, NC, (ea.nE + CTOT_ZF - 1) / CTOT_ZF), dim3(BLOCK), (size_t)side_pad, args)) return V2E_EHIP;
-            // a key row of a small grid is a couple of steps of one wave: one workgroup per frame; of a large grid (beyond a million
-            // pixels) a segmented scan by a workgroup of its own.  (1280x720 has 3 600 groups since the groups are 256 pixels: k_cframe1,
-            // 45 us per 32 frames; round 5 measured k_cframe there: 9.74 / 9.51 -> 8.89 / 9.02 Gev/s.)
-            if (h->ch_nwp <= 4096) {
-                if (sc.kernel(tab_stream, (const void *)k_cframe1, dim3(1, NC, ea.nE), dim3(CFRAME_THREADS), 0, args)) return V2E_EHIP;
-            } else if (sc.kernel(tab_stream, (const void *)k_cframe, dim3(std::min(h->nkeys_cap, CFRAME_ROWS), NC, ea.nE), dim3(CFRAME_THREADS), 0, args)) {
-                return V2E_EHIP;
-            }
+        // NSET table sets rotate: tables(b + 1) are built while k_cemit(b) reads those of b; k_cemit(b - NSET), which read this set
+        // last, is waited for (captured: it is on the same stream)
+        if (sc.wait(tab_stream, EV_FORK, b)) return V2E_EHIP;
+        if (b >= NSET && !captured && sc.wait(tab_stream, EV_JOIN, b - NSET)) return V2E_EHIP;
+        if (sc.kernel(tab_stream, (const void *)k_ctot, dim3(egx, NC, (ea.nE + CTOT_ZF - 1) / CTOT_ZF), dim3(BLOCK), 0, args)) return V2E_EHIP;
+        // a key row of a small grid is a couple of steps of one wave: one workgroup per frame; of a large grid (beyond a million
+        // pixels) a segmented scan by a workgroup of its own.  (1280x720 has 3 600 groups since the groups are 256 pixels: k_cframe1,
+        // 45 us per 32 frames; round 5 measured k_cframe there: 9.74 / 9.51 -> 8.89 / 9.02 Gev/s.)
+        if (h->ch_nwp <= 4096) {
+            if (sc.kernel(tab_stream, (const void *)k_cframe1, dim3(1, NC, ea.nE), dim3(CFRAME_THREADS), 0, args)) return V2E_EHIP;
+        } else if (sc.kernel(tab_stream, (const void *)k_cframe, dim3(std::min(h->nkeys_cap, CFRAME_ROWS), NC, ea.nE), dim3(CFRAME_THREADS), 0, args)) {
+            return V2E_EHIP;
         }
-        // rows: two batches side by side on two streams (the rows of a batch depend on nothing but its tables; the batch's
-        // event offset then comes from k_coff behind the tables); on one stream with the tables the rows carry it forward
-        const int row_stream = rows_own ? ST_SIDE2 : ((tab_stream == ST_SIDE || tab_stream == ST_MAIN || one_row_stream || pipelined) ? ST_SIDE : ((b & 1) ? ST_SIDE2 : ST_SIDE));
-        if (!no_emit && !ea.coff_in_cemit) {
+        const int row_stream = pipelined ? ST_SIDE2 : captured ? ST_SIDE : ((b & 1) ? ST_SIDE2 : ST_SIDE);
+        if (!ea.coff_in_cemit) {
             void *oargs[] = {(void *)&ea};
             if (sc.kernel(tab_stream, (const void *)k_coff, dim3(NC), dim3(WAVE), 0, oargs)) return V2E_EHIP;
         }
         if (sc.record(EV_TAB, b, tab_stream)) return V2E_EHIP;
-        if (row_stream != tab_stream && sc.wait(row_stream, EV_TAB, b)) return V2E_EHIP;
-        if (mark(ev_side, sc.st[row_stream])) return V2E_EHIP;
+        if (!captured && sc.wait(row_stream, EV_TAB, b)) return V2E_EHIP;
+        if (mark(true, sc.st[row_stream])) return V2E_EHIP;
         if (pull) {
             if (sc.kernel(row_stream, ea.cpre16 ? (const void *)k_cpull<true> : (const void *)k_cpull<false>, dim3(8 * ea.wpf * ((ea.nE + 7) / 8), NC), dim3(BLOCK), (size_t)(2 * ea.p2 * 4), args)) return V2E_EHIP;
-        } else if (!no_emit && sc.kernel(row_stream, (const void *)k_cemit, dim3(egx, NC, ea.nE), dim3(BLOCK), (size_t)std::max(REC_LDS, side_pad), args)) return V2E_EHIP;
-        if (mark(ev_side, sc.st[row_stream])) return V2E_EHIP;
+        } else if (sc.kernel(row_stream, (const void *)k_cemit, dim3(egx, NC, ea.nE), dim3(BLOCK), (size_t)REC_LDS, args)) return V2E_EHIP;
+        if (mark(true, sc.st[row_stream])) return V2E_EHIP;
         return sc.record(EV_JOIN, b, row_stream);
     };
     // Batch 0 of a run is split at the first chain launch's frames: the chain starts after the records of K frames, not of E
     // (its first launch idled through the whole first k_ahead: ~15 us of every 300-frame step); the rest of the batch follows on
     // the same stream and is waited for by the batch's other launches (event slot nL of EV_AHEAD: the batches use 0 .. nEB - 1).
-    constexpr bool split_first_ahead = true;
-    // (pipelined runs: the head runs beside the run before, the chain never waits for it -- one k_ahead launch, one event and one wait
-    // fewer: profiles/r06_emulator_experiments.txt item 14)
-    const bool split0 = split_first_ahead && m > 1 && n_frames > K && !pipelined;
+    // (Pipelined runs: the head runs beside the run before, the chain never waits for it -- one k_ahead launch, one event and one wait
+    // fewer: profiles/r06_emulator_experiments.txt item 14.)
+    const bool split0 = m > 1 && n_frames > K && !pipelined;
     // Pipelined runs whose ring holds the whole run (n_frames <= D: 300 frames in five batches of 64): ONE k_ahead launch for the run, right
     // behind its upload and zero fills, and ONE wait of the chain for all of it -- in steady state it ran beside the run before.  Every
     // wait and every record on the chain's stream costs its next launch ~7 us even when the event has long completed (gap before a
@@ -2207,10 +2136,10 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
             if (f1 <= f0) continue;
             AheadArgs aa;
             memset(&aa, 0, sizeof(aa));
-            aa.frames_pp = h->run_frames; aa.frame_stride = (unsigned long long)NC * h->npx * esz;
-            aa.ctl = h->run_ctl; aa.fidx_base = h->run_fidx;
+            aa.frames_pp = r.run_frames; aa.frame_stride = (unsigned long long)NC * h->npx * esz;
+            aa.ctl = r.run_ctl; aa.fidx_base = r.run_fidx;
             aa.f0 = f0; aa.nf = f1 - f0; aa.D = D; aa.n_clips = NC; aa.slot0 = f0 % D;
-            aa.rec = h->ch_rec;
+            aa.rec = r.ch_rec;
             // frame pairs per thread: a thread's set-up (thresholds, two divisions, the seed's ten Philox round keys) is paid once per
             // thread, so a thread takes several pairs -- as many as leave ~4 workgroups per CU (346x260, 64 frames: 3 z-blocks of 11 pairs;
             // round 6, A/B x 3 in one session: 1 pair 683-689 us per step, 4: 668-676, 11: 665-670, 16: 663-671; k_ahead's instructions
@@ -2222,7 +2151,7 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
                 aa.ppt = (pairs + zb - 1) / zb;
             }
             void *args[] = {(void *)&a, (void *)&aa};
-            if (sc.kernel(ST_AHEAD, (const void *)k_ahead<uint8_t>, dim3(h->ngroups, NC, (aa.nf / 2 + 1 + aa.ppt - 1) / aa.ppt), dim3(BLOCK), (size_t)side_pad, args)) return V2E_EHIP;
+            if (sc.kernel(ST_AHEAD, (const void *)k_ahead<uint8_t>, dim3(h->ngroups, NC, (aa.nf / 2 + 1 + aa.ppt - 1) / aa.ppt), dim3(BLOCK), 0, args)) return V2E_EHIP;
             if (sc.record(EV_AHEAD, part == 0 ? b : nL, ST_AHEAD)) return V2E_EHIP;
         }
         return 0;
@@ -2230,24 +2159,22 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
     // state planes: X[0] the caller's (bound) planes, X[1] the engine's second set; launch L reads X[L % 2], writes X[(L + 1) % 2]
     void *xb[2] = {h->base, has_refr ? h->ch_base2 : h->base}, *xl[2] = {h->lp, has_refr ? h->ch_lp2 : h->lp};
     float *xt[2] = {h->ts_mem, has_refr ? h->ch_ts2 : h->ts_mem};
-    // the run's uploads (frame times, first frame index) and the zero fills precede everything
-    constexpr bool no_side_fork = true; // under capture the side stream joins at its first batch
-    // The zero fill precedes the fork.  (Round 5 tried the fork first -- k_ahead touches nothing the fill clears -- and lost 10 %:
+    // The run's zero fills precede the fork.  (Round 5 tried the fork first -- k_ahead touches nothing the fill clears -- and lost 10 %:
     // 12.0 -> 10.8 Gev/s, A/B x 3 in one session; the enqueue order of a capture decides which branches this runtime overlaps,
     // profiles/r03_graph_scheduling.txt.)
     {   // one launch: the run's records, batch 0's event offset, and (refractory runs) the rule-on maxima and rendezvous counters
-        void *const zp[4] = {recs, h->run_off, has_refr ? (void *)h->ch_gM : nullptr, has_refr ? (void *)h->ch_bar : nullptr};
+        void *const zp[4] = {recs, r.run_off, has_refr ? (void *)r.ch_gM : nullptr, has_refr ? (void *)r.ch_bar : nullptr};
         const size_t zb[4] = {sizeof(v2e_frame_rec) * (size_t)n_frames * NC, sizeof(unsigned long long) * NC,
                               sizeof(uint32_t) * (size_t)nL * (K + 1) * NC * K, sizeof(unsigned) * (size_t)nL * 2 * K * NC};
         if (sc.zero4(pipelined ? ST_AHEAD : ST_MAIN, zp, zb)) return V2E_EHIP;
     }
     // (pipelined: no forks -- the k_ahead stream carries the run's upload and zero fills itself and runs ahead of the chain, the
-    // emission stream waits for the chain batch by batch)
+    // emission streams wait for the chain batch by batch; captured: the side stream joins at its first batch)
     if (!pipelined) {
-    if (sc.record(EV_FORK, nL, ST_MAIN)) return V2E_EHIP;
-    if (!(capturing && no_side_fork) && sc.wait(ST_SIDE, EV_FORK, nL)) return V2E_EHIP;
-    if (!fused_rec && sc.wait(ST_AHEAD, EV_FORK, nL)) return V2E_EHIP;
-    if (!capturing && (sc.wait(ST_TAB, EV_FORK, nL) || sc.wait(ST_SIDE2, EV_FORK, nL))) return V2E_EHIP;
+        if (sc.record(EV_FORK, nL, ST_MAIN)) return V2E_EHIP;
+        if (!captured && sc.wait(ST_SIDE, EV_FORK, nL)) return V2E_EHIP;
+        if (!fused_rec && sc.wait(ST_AHEAD, EV_FORK, nL)) return V2E_EHIP;
+        if (!captured && (sc.wait(ST_TAB, EV_FORK, nL) || sc.wait(ST_SIDE2, EV_FORK, nL))) return V2E_EHIP;
     }
     int last_ahead = -1; // the last k_ahead batch this piece enqueued (joined at the end)
     if (ahead_whole && launch_ahead(0)) return V2E_EHIP; // (all of the run's records: before the one event the chain waits for)
@@ -2257,38 +2184,35 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
         last_ahead = b;
     }
     // last batch in two pieces: only where the last launch is not the first of its batch (else there is nothing to emit early)
-    constexpr bool split_tail_env = true;
     const int tail_f0 = (nB - 1) * K;                          // first frame of the last chain launch with frames
     // (pipelined runs: the last emission finishes beside the next run's chain -- one piece, six API calls fewer)
-    const bool split_tail = split_tail_env && has_refr && m > 1 && nB >= 2 && (nB - 1) % m != 0 && !no_emit_run && !pipelined;
+    const bool split_tail = has_refr && m > 1 && nB >= 2 && (nB - 1) % m != 0 && !pipelined;
     int last_emitted = -1; // the last emission slot this piece enqueued (joined at the end)
-    constexpr int allon_env = 1;
-    const bool allon = allon_env && a_in.has_cutoff && a_in.do_leak && a_in.do_shot && a_in.has_refr;
+    const bool allon = a_in.has_cutoff && a_in.do_leak && a_in.do_shot && a_in.has_refr;
     const void *kfn = chain_fn(p->f64_state != 0, dtype, fused_rec, allon);
     for (int L = 0; L < nL; ++L) {
         const ChainLaunch &pl = plan[L];
         const bool tail = pl.nf == 0;
         ChainArgs ca;
         memset(&ca, 0, sizeof(ca));
-        ca.frames_pp = h->run_frames; ca.frame_stride = (unsigned long long)NC * h->npx * esz; ca.fidx_base = h->run_fidx;
-        ca.ctl = h->run_ctl;
+        ca.frames_pp = r.run_frames; ca.frame_stride = (unsigned long long)NC * h->npx * esz; ca.fidx_base = r.run_fidx;
+        ca.ctl = r.run_ctl;
         ca.f0 = pl.f0; ca.nf = pl.nf; ca.pf0 = pl.pf0; ca.pnf = pl.pnf;
         ca.D = D; ca.n_clips = NC; ca.K = K; ca.ngroups = h->ngroups;
         ca.slot_f0 = pl.f0 % D; ca.slot_pf0 = pl.pf0 % D;
-        ca.cnt = h->ch_cnt; ca.ruleM = h->ch_ruleM; ca.tsold = has_refr ? h->ch_tsold : nullptr;
-        ca.rec = h->ch_rec;
+        ca.cnt = r.ch_cnt; ca.ruleM = r.ch_ruleM; ca.tsold = has_refr ? r.ch_tsold : nullptr;
+        ca.rec = r.ch_rec;
         if (has_refr) {
-            ca.gM_cur = h->ch_gM + (size_t)L * (K + 1) * NC * K;
-            ca.gM_prev = h->ch_gM + (size_t)(L > 0 ? L - 1 : 0) * (K + 1) * NC * K;
-            ca.bar_prev = h->ch_bar + (size_t)(L > 0 ? L - 1 : 0) * 2 * K * NC;
+            ca.gM_cur = r.ch_gM + (size_t)L * (K + 1) * NC * K;
+            ca.gM_prev = r.ch_gM + (size_t)(L > 0 ? L - 1 : 0) * (K + 1) * NC * K;
+            ca.bar_prev = r.ch_bar + (size_t)(L > 0 ? L - 1 : 0) * 2 * K * NC;
         }
         const int in = L % 2, out = tail ? 0 : (L + 1) % 2, pin = (L + 1) % 2;
         ca.base_in = xb[in]; ca.lp_in = xl[in]; ca.ts_in = xt[in];
         ca.base_fix = xb[in]; ca.lp_fix = xl[in]; ca.ts_fix = xt[in];
         ca.base_out = xb[out]; ca.lp_out = xl[out]; ca.ts_out = xt[out];
         ca.base_pin = xb[pin]; ca.lp_pin = xl[pin]; ca.ts_pin = xt[pin];
-        constexpr bool no_ckpt = false;
-        if (has_refr && K > CHAIN_SUB && h->ch_ck && !no_ckpt) {
+        if (has_refr && K > CHAIN_SUB && h->ch_ck) {
             const size_t plane = (size_t)(K / CHAIN_SUB - 1 + (K % CHAIN_SUB ? 1 : 0)) * NC * h->npx_pad; // elements per (parity, quantity): a checkpoint before frames 8, 16, ...
             auto ck = [&](int par, char *&bp, char *&lpp, float *&tp) {
                 char *q = (char *)h->ch_ck + (size_t)par * plane * 20;
@@ -2302,25 +2226,22 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
         }
         ca.recs = recs;
         ca.store_out = tail && in != 0;
-        ca.prio = chain_prio;
-        ca.bar_light = bar_light;
-        ca.lockstep = lockstep;
+        ca.prio = 3;      // wave priority of the chain (measured against 0 in round 3)
+        ca.bar_light = 1; // the fence-free rendezvous (round 4; the fenced one of round 3 is still in clip_barrier)
+        ca.lockstep = 0;  // lock-step redo passes (emu_chain.h, V2E_CHAIN_LOCKSTEP): 10.4-10.6 against 10.8-11.0 Gev/s on the benchmark clip (round 4)
         ca.dbg = (h->dbg && L == nB / 2) ? h->dbg : nullptr;
-        ca.stamp_pp = h->stamp_slot; ca.lidx = std::min(L, STAMP_LAUNCHES - 1);
+        ca.stamp_pp = r.stamp_slot; ca.lidx = std::min(L, STAMP_LAUNCHES - 1);
         if (pl.wait_join >= 0 && sc.wait(ST_MAIN, EV_JOIN, pl.wait_join)) return V2E_EHIP; // ring slots: read by k_cemit of that batch
-        // (records of batches 0 and 1 without the head piece in this enqueue: the caller ordered this piece behind the head's stream)
         if (!ahead_whole && pl.wait_ahead >= 0 && sc.wait(ST_MAIN, EV_AHEAD, pl.wait_ahead)) return V2E_EHIP;
         if (split0 && !fused_rec && !tail && L >= 1 && L < m && sc.wait(ST_MAIN, EV_AHEAD, nL)) return V2E_EHIP; // the rest of batch 0
-        if (mark(ev_main, s)) return V2E_EHIP; // instrumented runs: an event before and after every chain launch
+        if (mark(false, s)) return V2E_EHIP; // profiled runs: an event before and after every chain launch
         void *args[] = {(void *)&a, (void *)&ca};
         if (sc.kernel(ST_MAIN, kfn, grid, dim3(BLOCK), chain_dyn_lds(fused_rec), args)) return V2E_EHIP;
-        if (mark(ev_main, s)) return V2E_EHIP;
+        if (mark(false, s)) return V2E_EHIP;
         if (!ahead_whole && !fused_rec && L % m == 0 && sc.record(EV_CHAIN, L, ST_MAIN)) return V2E_EHIP; // (what a later k_ahead batch waits for where the ring wraps)
-        // Enqueue order of the two side branches: k_ahead first.  It decides how this runtime executes the captured graph:
-        // with the emission enqueued first the chain's next launch runs BEHIND the emission kernels (measured, profiles/
-        // r03_graph_scheduling.txt), with k_ahead first it runs beside them.
-        constexpr bool ahead_first = true;
-        if (ahead_first && !ahead_whole && pl.ahead_next >= 0) { if (launch_ahead(pl.ahead_next)) return V2E_EHIP; last_ahead = pl.ahead_next; }
+        // k_ahead before the emission: the enqueue order decides how this runtime executes the captured graph -- with the emission
+        // first the chain's next launch runs BEHIND the emission kernels, with k_ahead first beside them (profiles/r03_graph_scheduling.txt)
+        if (!ahead_whole && pl.ahead_next >= 0) { if (launch_ahead(pl.ahead_next)) return V2E_EHIP; last_ahead = pl.ahead_next; }
         if (split_tail && L == nB - 1 && tail_f0 > (nEB - 1) * E) {
             if (sc.record(EV_FORK, nEB - 1, ST_MAIN)) return V2E_EHIP;
             if (launch_emission(nEB - 1, (nEB - 1) * E, tail_f0 - (nEB - 1) * E)) return V2E_EHIP;
@@ -2337,12 +2258,11 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
             if (launch_emission(pl.emit_batch, pl.emit_batch * E, std::min((pl.emit_batch + 1) * E, n_frames) - pl.emit_batch * E)) return V2E_EHIP;
             last_emitted = pl.emit_batch;
         }
-        if (!ahead_first && !ahead_whole && pl.ahead_next >= 0) { if (launch_ahead(pl.ahead_next)) return V2E_EHIP; last_ahead = pl.ahead_next; }
     }
-    if (!graph && !pipelined) { // join: the piece is complete on `s` (a graph is complete when all its nodes are)
+    if (!pipelined) { // join: the run is complete on `s`
         if (last_emitted >= 0 && sc.wait(ST_MAIN, EV_JOIN, last_emitted)) return V2E_EHIP;
-        if (!capturing && last_emitted >= 0 && sc.wait(ST_MAIN, EV_TAB, last_emitted)) return V2E_EHIP;
-        if (!capturing && last_emitted >= 1 && sc.wait(ST_MAIN, EV_JOIN, last_emitted - 1)) return V2E_EHIP;
+        if (!captured && last_emitted >= 0 && sc.wait(ST_MAIN, EV_TAB, last_emitted)) return V2E_EHIP;
+        if (!captured && last_emitted >= 1 && sc.wait(ST_MAIN, EV_JOIN, last_emitted - 1)) return V2E_EHIP;
         if (!fused_rec && last_ahead >= 0 && sc.wait(ST_MAIN, EV_AHEAD, last_ahead)) return V2E_EHIP;
     }
     V2E_HIP(hipGetLastError());
@@ -2444,197 +2364,182 @@ static int assign_pipelined_streams(v2e_emu *h, hipStream_t s)
     return 0;
 }
 
-int v2e_emu_run(v2e_emu *h, const v2e_emu_params *p, const void *frames, int dtype, int n_frames, const double *t_prev,
-                const double *t_frame, uint32_t frame_idx0, float *events, uint64_t cap, v2e_frame_rec *recs_dev,
-                int use_graph, void *stream)
+// ---- v2e_emu_run, one function per mode
+// Everything a run's kernels read that is sized by its length: the two pinned staging sets (all scratch sets' device buffers go with
+// them) and the current set's device buffer.
+static int reserve_run(v2e_emu *h, int n_frames, hipStream_t s)
 {
-    int rc = check_params(h, p);
-    if (rc) return rc;
-    V2E_REQUIRE(p->rng_mode == V2E_RNG_PHILOX, "v2e_emu_run is the device-resident Philox path");
-    V2E_REQUIRE(frames && t_prev && t_frame && events && recs_dev && n_frames > 0, "bad run args");
-    V2E_REQUIRE(dtype == V2E_DT_U8 || dtype == V2E_DT_F32 || dtype == V2E_DT_F64, "bad frame dtype");
-    V2E_REQUIRE(!h->cs_sur || ((int)h->csr_steps.size() == n_frames && h->n_clips == 1),
-                "a run with a CSDVS surround needs v2e_emu_set_csdvs_run for exactly these frames (one clip)");
-    V2E_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
     if (n_frames > h->run_cap) {
         h->sync_runs();
         V2E_HIP(hipStreamSynchronize(s));
-        if (h->run_ctl) V2E_HIP(hipFree(h->run_ctl));
-        hipFree(h->alt_of((void **)&h->run_ctl));
-        h->run_ctl = nullptr; h->alt_of((void **)&h->run_ctl) = nullptr;
+        for (RunScratch &r : h->sets) { hipFree(r.run_ctl); r.run_ctl = nullptr; }
         for (int q = 0; q < 2; ++q) if (h->run_ctl_host2[q]) V2E_HIP(hipHostFree(h->run_ctl_host2[q]));
         h->run_cap = n_frames;
         for (int q = 0; q < 2; ++q) V2E_HIP(hipHostMalloc(&h->run_ctl_host2[q], sizeof(FrameCtl) * (size_t)h->run_cap * h->n_clips));
         h->drop_graphs();
     }
-    KArgs a = make_kargs(h, p);
-    const int mode = use_graph & 3;          // 0 plain launches, 1 hipGraph, 2 instrumented
-    // K frames per launch with the state in registers (emu_chain.h) wherever it can run: |256 insists on it; |16 selects the
-    // count / rank / scan / emit kernels one frame at a time (kept for A/B; also what carries the photoreceptor-noise plane,
-    // emulator.py:694-703, float64 log-encoded frames and more than CHAIN_MAX_ITERS events per pixel and frame)
-    const bool chain_ok = chain_eligible(h, p, dtype);
-    V2E_REQUIRE(!(use_graph & 256) || chain_ok, "k_chain cannot run this configuration (max_iters, photoreceptor noise or float64 log frames)");
-    const bool chain = chain_ok && ((use_graph & 256) != 0 || !(use_graph & 16));
-    const bool legacy = !chain;
-    // mode 0 | 1024: PIPELINED runs (round 6) -- plain launches on four streams, no graph, no join at the run's end.  The chain of run
-    // n + 1 needs the chain of run n and nothing else of it, but a run begins with an upload, zero fills and its first records (k_ahead)
-    // and ends with the emission of its last frames: measured with the device stamps (v2e_emu_launch_stamps), 145-165 us of every
-    // 820 us step of the benchmark passed between the last chain launch of one run and the first of the next (a graph's end and start
-    // cost two cross-queue hops of 20-50 us each on this runtime, and everything of a graph must be complete before the next one
-    // starts).  Pipelined: the caller's stream carries the chain's launches and nothing else, run after run in one hardware queue
-    // (33 us between two runs' chains); the handle's k_ahead stream carries the run's upload, zero fills and records and runs AHEAD of
-    // the chain, beside the run before; the handle's emission stream follows the chain batch by batch and finishes beside the run
-    // after.  What two runs in flight would share exists twice (v2e_emu::swap_scratch): such a run takes the set the run before it did not.
-    const bool pipelined = (use_graph & 1024) != 0 && mode == 0 && chain;
-    if (pipelined) h->swap_scratch();
-    h->last_ticket = pipelined ? h->scratch_par : -1;
-    if (!h->run_ctl) { V2E_HIP(hipMalloc(&h->run_ctl, sizeof(FrameCtl) * (size_t)h->run_cap * h->n_clips)); h->drop_graphs(); }
-    if (chain) {
-        rc = chain_alloc(h, p, dtype, n_frames, use_graph);
-        if (rc) return rc;
-    }
-    if (pipelined && (!h->probed || h->probed_for != s)) {
-        rc = assign_pipelined_streams(h, s);
-        if (rc) return rc;
-    }
-    const int par = h->scratch_par;
-    hipStream_t s_up = s; // the stream of the run's upload
-    if (pipelined) {
-        for (int q = 0; q < 2; ++q) {
-            if (!h->ev_main_done2[q]) V2E_HIP(hipEventCreateWithFlags(&h->ev_main_done2[q], hipEventDisableTiming));
-            if (!h->ev_tail_done2[q]) V2E_HIP(hipEventCreateWithFlags(&h->ev_tail_done2[q], hipEventDisableTiming));
-        }
-        s_up = h->ahead; // (created by chain_alloc)
-        // the k_ahead stream reads the frames: it is ordered behind what the caller's stream holds now -- unless the caller vouches
-        // that the frames are resident (|2048: nothing enqueued on `stream` still writes them); otherwise it would wait for the chain
-        // of the run before, which is on that stream, and the run's head would not overlap it
-        if (!(use_graph & 2048)) {
-            if (!h->ev_user) V2E_HIP(hipEventCreateWithFlags(&h->ev_user, hipEventDisableTiming));
-            V2E_HIP(hipEventRecord(h->ev_user, s));
-            V2E_HIP(hipStreamWaitEvent(s_up, h->ev_user, 0));
-        }
-        // this scratch set's last user (two runs ago): its chain and its emission have finished
-        if (h->piece_pending[par]) {
-            V2E_HIP(hipStreamWaitEvent(s_up, h->ev_main_done2[par], 0));
-            V2E_HIP(hipStreamWaitEvent(s_up, h->ev_tail_done2[par], 0));
-        }
-        if (h->piece_pending[par ^ 1] && (events == h->last_events || (const void *)recs_dev == h->last_recs))
-            V2E_HIP(hipStreamWaitEvent(s_up, h->ev_tail_done2[par ^ 1], 0));
-    } else if (h->join_runs(s)) { // everything else runs whole on the caller's stream, behind every piece still in flight
-        v2e_set_error("hipStreamWaitEvent failed");
-        return V2E_EHIP;
-    }
-    // two pinned staging sets, each guarded by the event of the upload that last read it: the host prepares run n + 1
-    // while run n executes
+    RunScratch &r = h->cur();
+    if (!r.run_ctl) { V2E_HIP(hipMalloc(&r.run_ctl, sizeof(FrameCtl) * (size_t)h->run_cap * h->n_clips)); h->drop_graphs(); }
+    return 0;
+}
+
+// The run's frame times, first frame index, frames' address and stamp slot to the current scratch set's device variables, on `s_up`:
+// through k_upload_ctl, which reads one of two pinned staging sets (round 5; before: three hipMemcpyAsync -- A/B x 3 on the benchmark
+// loop 11.9 -> 12.15 Gev/s: in the rocprofv3 timeline the copy-engine upload started 40-90 us behind the command before it, the kernel
+// 10 us).  Each staging set is guarded by the event of the upload that last read it: the host prepares run n + 1 while run n executes.
+static int upload_run(v2e_emu *h, const v2e_emu_params *p, int n_frames, const double *t_prev, const double *t_frame,
+                      uint32_t frame_idx0, const void *frames, hipStream_t s_up)
+{
+    const RunScratch &r = h->cur();
     const int sq = h->run_stage ^= 1;
     if (!h->ev_stage[sq]) V2E_HIP(hipEventCreateWithFlags(&h->ev_stage[sq], hipEventDisableTiming));
     else V2E_HIP(hipEventSynchronize(h->ev_stage[sq]));
-    FrameCtl *ctl_host = h->run_ctl_host2[sq];
-    uint32_t *fidx_host = h->run_fidx_host + sq;
+    static_assert(sizeof(FrameCtl) >= 2 * sizeof(double), "the staging set holds two doubles per frame");
     const size_t nct = (size_t)n_frames * h->n_clips;
-    double *const tp_host = (double *)ctl_host, *const tf_host = tp_host + nct; // (the staging set holds the frame times)
+    double *const tp_host = (double *)h->run_ctl_host2[sq], *const tf_host = tp_host + nct;
     memcpy(tp_host, t_prev, sizeof(double) * nct);
     memcpy(tf_host, t_frame, sizeof(double) * nct);
+    uint32_t *fidx_host = h->run_fidx_host + sq;
     *fidx_host = frame_idx0;
     const void **frames_host = h->run_frames_host + sq; // the chain pipeline reads the frames' address from a device variable:
     *frames_host = frames;                              // runs over different frame buffers replay the same captured graph
-    // The run's frame scalars, first frame index and frames' address go up through a kernel that reads the pinned staging set
-    // (round 5; before: three hipMemcpyAsync).  A/B x 3 in one session on the benchmark loop: 11.9 -> 12.15 Gev/s -- in the rocprofv3
-    // timeline the copy-engine upload started 40-90 us behind the command before it, the kernel 10 us.
-    {
-        static_assert(sizeof(FrameCtl) >= 2 * sizeof(double), "the staging set holds two doubles per frame");
-        unsigned long long **slot_host = h->stamp_slot_host + sq;
-        *slot_host = h->stamps_runs > 0 ? h->stamps + (size_t)(h->stamp_seq++ % (unsigned long long)h->stamps_runs) * 2 * STAMP_LAUNCHES : nullptr;
-        k_upload_ctl<<<(unsigned)std::min<size_t>((nct + BLOCK - 1) / BLOCK, 1024), BLOCK, 0, s_up>>>(tp_host, tf_host, h->run_ctl, nct, p->cutoff_hz, p->shot_noise_rate_hz,
-                                                                                                   p->refractory_period_s, fidx_host, h->run_fidx, frames_host, h->run_frames,
-                                                                                                   slot_host, h->stamp_slot);
-        V2E_HIP(hipGetLastError());
-    }
+    unsigned long long **slot_host = h->stamp_slot_host + sq;
+    *slot_host = h->stamps_runs > 0 ? h->stamps + (size_t)(h->stamp_seq++ % (unsigned long long)h->stamps_runs) * 2 * STAMP_LAUNCHES : nullptr;
+    k_upload_ctl<<<(unsigned)std::min<size_t>((nct + BLOCK - 1) / BLOCK, 1024), BLOCK, 0, s_up>>>(tp_host, tf_host, r.run_ctl, nct, p->cutoff_hz, p->shot_noise_rate_hz,
+                                                                                               p->refractory_period_s, fidx_host, r.run_fidx, frames_host, r.run_frames,
+                                                                                               slot_host, r.stamp_slot);
+    V2E_HIP(hipGetLastError());
     V2E_HIP(hipEventRecord(h->ev_stage[sq], s_up));
-    h->last_kind = legacy ? 0 : (h->ch_fused ? 4 : 3);
-    h->last_fpl = chain ? h->ch_K : 1;
-    h->last_fpb = chain ? h->ch_E : 1;
-    if (mode == 0) {
-        if (legacy) return enqueue_run(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, s, nullptr);
-        if (!pipelined) return enqueue_run_chain(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, s);
-        rc = enqueue_run_chain(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, s, nullptr, nullptr, nullptr, false, true);
-        if (rc) return rc;
-        V2E_HIP(hipEventRecord(h->ev_main_done2[par], s));          // the run's chain (the pixel state)
-        hipStream_t rows_stream = h->side2;
-        // the run's records to pinned host memory behind its last rows (v2e_emu_run_recs): what result() reads -- no copy of the
-        // caller's own, no stream of the caller's to synchronise
-        const size_t rbytes = sizeof(v2e_frame_rec) * (size_t)n_frames * h->n_clips;
-        if (rbytes > h->recs_host_cap[par]) {
-            if (h->recs_host[par]) V2E_HIP(hipHostFree(h->recs_host[par]));
-            h->recs_host[par] = nullptr;
-            V2E_HIP(hipHostMalloc(&h->recs_host[par], rbytes));
-            h->recs_host_cap[par] = rbytes;
-        }
-        V2E_HIP(hipMemcpyAsync(h->recs_host[par], recs_dev, rbytes, hipMemcpyDeviceToHost, rows_stream));
-        h->recs_host_n[par] = (size_t)n_frames * h->n_clips;
-        V2E_HIP(hipEventRecord(h->ev_tail_done2[par], rows_stream)); // its last event rows (and the records' copy)
-        h->piece_pending[par] = true;
-        h->last_events = events; h->last_recs = recs_dev;
-        return 0;
-    }
-    if (mode == 2 && chain) { // instrumented: chain time from events on `s`, emission batches from events on the side stream
-        std::vector<hipEvent_t> em, es;
-        rc = enqueue_run_chain(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, s, nullptr, &em, &es);
-        if (rc == 0) {
-            V2E_HIP(hipStreamSynchronize(s));
-            for (int k = 0; k < 4; ++k) h->prof_ms[k] = 0.0;
-            float ms = 0.f;
-            V2E_HIP(hipEventElapsedTime(&ms, em.front(), em.back()));
-            h->prof_ms[0] = ms; // first launch's start to last launch's end: the chain's launch-to-launch period x launches
-            h->prof_chain_us.clear();
-            for (size_t i = 0; i + 1 < em.size(); i += 2) { // the kernels alone
-                V2E_HIP(hipEventElapsedTime(&ms, em[i], em[i + 1]));
-                h->prof_ms[1] += ms;
-                h->prof_chain_us.push_back(ms * 1e3f);
-            }
-            h->prof_step_launches = (int)(em.size() / 2);
-            for (size_t i = 0; i + 1 < es.size(); i += 2) {
-                V2E_HIP(hipEventElapsedTime(&ms, es[i], es[i + 1]));
-                h->prof_ms[3] += ms;
-            }
-            h->prof_launches = n_frames;
-            h->prof_emit_batches = (int)(es.size() / 2);
-        }
-        for (hipEvent_t e : em) hipEventDestroy(e);
-        for (hipEvent_t e : es) hipEventDestroy(e);
-        return rc;
-    }
-    if (mode == 2) { // instrumented: a hipEvent before every launch; blocking
-        const int ne = 4 * n_frames + 4;
-        std::vector<hipEvent_t> evs(ne);
-        for (int i = 0; i < ne; ++i) V2E_HIP(hipEventCreate(&evs[i]));
-        rc = enqueue_run(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, s, evs.data());
-        if (rc == 0) {
-            V2E_HIP(hipStreamSynchronize(s));
-            for (int k = 0; k < 4; ++k) h->prof_ms[k] = 0.0;
-            for (int i = 0; i < 4 * n_frames; ++i) {
-                float ms = 0.f;
-                V2E_HIP(hipEventElapsedTime(&ms, evs[i], evs[i + 1]));
-                h->prof_ms[i & 3] += ms;
-            }
-            h->prof_launches = n_frames;
-            h->prof_emit_batches = 0;
-            h->prof_step_launches = n_frames;
-        }
-        for (int i = 0; i < ne; ++i) hipEventDestroy(evs[i]);
-        return rc;
-    }
+    return 0;
+}
 
-    // graph path: everything baked into the graph is part of the cache key
+// PIPELINED runs (round 6).  The chain of run n + 1 needs the chain of run n and nothing else of it, but a run begins with an upload,
+// zero fills and its first records (k_ahead) and ends with the emission of its last frames: measured with the device stamps
+// (v2e_emu_launch_stamps), 145-165 us of every 820 us step of the benchmark passed between the last chain launch of one run and the
+// first of the next with one graph per run.  Here the caller's stream carries the chain's launches only, run after run in one hardware
+// queue (33 us between two runs' chains); the handle's k_ahead stream carries the run's head and runs ahead of the chain, beside the
+// run before; the emission streams follow the chain batch by batch and finish beside the run after.  The run has scratch set `par`.
+static int run_pipelined(v2e_emu *h, const v2e_emu_params *p, const KArgs &a, const void *frames, int dtype, int n_frames,
+                         const double *t_prev, const double *t_frame, uint32_t frame_idx0, float *events, uint64_t cap,
+                         v2e_frame_rec *recs_dev, bool frames_resident, hipStream_t s)
+{
+    if (!h->probed || h->probed_for != s) {
+        const int rc = assign_pipelined_streams(h, s);
+        if (rc) return rc;
+    }
+    const int par = h->scratch_par;
+    for (int q = 0; q < 2; ++q) {
+        if (!h->ev_main_done2[q]) V2E_HIP(hipEventCreateWithFlags(&h->ev_main_done2[q], hipEventDisableTiming));
+        if (!h->ev_tail_done2[q]) V2E_HIP(hipEventCreateWithFlags(&h->ev_tail_done2[q], hipEventDisableTiming));
+    }
+    hipStream_t s_up = h->ahead; // the run's head
+    // the k_ahead stream reads the frames: it is ordered behind what the caller's stream holds now -- unless the caller vouches that
+    // the frames are resident; otherwise it would wait for the chain of the run before, which is on that stream, and the run's head
+    // would not overlap it
+    if (!frames_resident) {
+        if (!h->ev_user) V2E_HIP(hipEventCreateWithFlags(&h->ev_user, hipEventDisableTiming));
+        V2E_HIP(hipEventRecord(h->ev_user, s));
+        V2E_HIP(hipStreamWaitEvent(s_up, h->ev_user, 0));
+    }
+    // this scratch set's last user (two runs ago): its chain and its emission have finished
+    if (h->piece_pending[par]) {
+        V2E_HIP(hipStreamWaitEvent(s_up, h->ev_main_done2[par], 0));
+        V2E_HIP(hipStreamWaitEvent(s_up, h->ev_tail_done2[par], 0));
+    }
+    if (h->piece_pending[par ^ 1] && (events == h->last_events || (const void *)recs_dev == h->last_recs))
+        V2E_HIP(hipStreamWaitEvent(s_up, h->ev_tail_done2[par ^ 1], 0));
+    int rc = upload_run(h, p, n_frames, t_prev, t_frame, frame_idx0, frames, s_up);
+    if (rc) return rc;
+    rc = enqueue_run_chain(h, p, a, dtype, n_frames, events, cap, recs_dev, s, ChainMode::pipelined);
+    if (rc) return rc;
+    V2E_HIP(hipEventRecord(h->ev_main_done2[par], s)); // the run's chain (the pixel state)
+    hipStream_t rows_stream = h->side2;
+    // the run's records to pinned host memory behind its last rows (v2e_emu_run_recs): what result() reads -- no copy of the
+    // caller's own, no stream of the caller's to synchronise
+    const size_t rbytes = sizeof(v2e_frame_rec) * (size_t)n_frames * h->n_clips;
+    if (rbytes > h->recs_host_cap[par]) {
+        if (h->recs_host[par]) V2E_HIP(hipHostFree(h->recs_host[par]));
+        h->recs_host[par] = nullptr;
+        V2E_HIP(hipHostMalloc(&h->recs_host[par], rbytes));
+        h->recs_host_cap[par] = rbytes;
+    }
+    V2E_HIP(hipMemcpyAsync(h->recs_host[par], recs_dev, rbytes, hipMemcpyDeviceToHost, rows_stream));
+    h->recs_host_n[par] = (size_t)n_frames * h->n_clips;
+    V2E_HIP(hipEventRecord(h->ev_tail_done2[par], rows_stream)); // its last event rows (and the records' copy)
+    h->piece_pending[par] = true;
+    h->last_events = events; h->last_recs = recs_dev;
+    return 0;
+}
+
+// V2E_RUN_PROFILE through k_chain (blocking): chain time from events on `s`, emission batches from events around the event rows
+static int run_profiled_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a, int dtype, int n_frames, float *events, uint64_t cap,
+                              v2e_frame_rec *recs_dev, hipStream_t s)
+{
+    ChainMarks mk;
+    int rc = enqueue_run_chain(h, p, a, dtype, n_frames, events, cap, recs_dev, s, ChainMode::profiled, &mk);
+    if (rc == 0) {
+        std::vector<hipEvent_t> &em = mk.chain, &es = mk.rows;
+        V2E_HIP(hipStreamSynchronize(s));
+        for (int k = 0; k < 4; ++k) h->prof_ms[k] = 0.0;
+        float ms = 0.f;
+        V2E_HIP(hipEventElapsedTime(&ms, em.front(), em.back()));
+        h->prof_ms[0] = ms; // first launch's start to last launch's end: the chain's launch-to-launch period x launches
+        h->prof_chain_us.clear();
+        for (size_t i = 0; i + 1 < em.size(); i += 2) { // the kernels alone
+            V2E_HIP(hipEventElapsedTime(&ms, em[i], em[i + 1]));
+            h->prof_ms[1] += ms;
+            h->prof_chain_us.push_back(ms * 1e3f);
+        }
+        h->prof_step_launches = (int)(em.size() / 2);
+        for (size_t i = 0; i + 1 < es.size(); i += 2) {
+            V2E_HIP(hipEventElapsedTime(&ms, es[i], es[i + 1]));
+            h->prof_ms[3] += ms;
+        }
+        h->prof_launches = n_frames;
+        h->prof_emit_batches = (int)(es.size() / 2);
+    }
+    for (hipEvent_t e : mk.chain) hipEventDestroy(e);
+    for (hipEvent_t e : mk.rows) hipEventDestroy(e);
+    return rc;
+}
+
+// V2E_RUN_PROFILE through the per-frame kernels (blocking): a hipEvent before every launch
+static int run_profiled_frames(v2e_emu *h, const v2e_emu_params *p, const KArgs &a, const void *frames, int dtype, int n_frames,
+                               float *events, uint64_t cap, v2e_frame_rec *recs_dev, hipStream_t s)
+{
+    const int ne = 4 * n_frames + 4;
+    std::vector<hipEvent_t> evs(ne);
+    for (int i = 0; i < ne; ++i) V2E_HIP(hipEventCreate(&evs[i]));
+    int rc = enqueue_run(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, s, evs.data());
+    if (rc == 0) {
+        V2E_HIP(hipStreamSynchronize(s));
+        for (int k = 0; k < 4; ++k) h->prof_ms[k] = 0.0;
+        for (int i = 0; i < 4 * n_frames; ++i) {
+            float ms = 0.f;
+            V2E_HIP(hipEventElapsedTime(&ms, evs[i], evs[i + 1]));
+            h->prof_ms[i & 3] += ms;
+        }
+        h->prof_launches = n_frames;
+        h->prof_emit_batches = 0;
+        h->prof_step_launches = n_frames;
+    }
+    for (int i = 0; i < ne; ++i) hipEventDestroy(evs[i]);
+    return rc;
+}
+
+// Everything a captured run bakes in (buffers, sizes, parameters, the current scratch set's pointers): the key of its cached graph
+static std::vector<unsigned char> graph_key(const v2e_emu *h, const v2e_emu_params *p, const KArgs &a, const void *frames, int dtype,
+                                            int n_frames, float *events, uint64_t cap, v2e_frame_rec *recs_dev, bool chain)
+{
+    const RunScratch &r = h->cur();
     std::vector<unsigned char> key;
     auto push = [&key](const void *ptr, size_t n) { const unsigned char *b = (const unsigned char *)ptr; key.insert(key.end(), b, b + n); };
     push(&a, sizeof(a)); push(&dtype, sizeof(dtype)); push(&n_frames, sizeof(n_frames));
-    if (legacy) push(&frames, sizeof(frames)); // the chain pipeline reads the frames' address from h->run_frames
+    if (!chain) push(&frames, sizeof(frames)); // the chain pipeline reads the frames' address from RunScratch::run_frames
     push(&events, sizeof(events)); push(&cap, sizeof(cap)); push(&recs_dev, sizeof(recs_dev));
     int f64 = p->f64_state; push(&f64, sizeof(f64));
-    int lg = legacy ? 1 : 3; push(&lg, sizeof(lg)); push(&h->dbg, sizeof(h->dbg));
-    push(&h->run_ctl, sizeof(h->run_ctl)); push(&h->run_fidx, sizeof(h->run_fidx)); push(&h->run_off, sizeof(h->run_off)); // (per scratch set)
+    int lg = chain ? 3 : 1; push(&lg, sizeof(lg)); push(&h->dbg, sizeof(h->dbg));
+    push(&r.run_ctl, sizeof(r.run_ctl)); push(&r.run_fidx, sizeof(r.run_fidx)); push(&r.run_off, sizeof(r.run_off));
     { const int mk = h->stamps_runs > 0 ? 1 : 0; push(&mk, sizeof(mk)); }
     if (h->cs_sur) { // everything the diffuser's launches bake in
         push(&h->cs_sur, sizeof(h->cs_sur)); push(&h->csr_scratch, sizeof(void *)); push(&h->csr_lp, sizeof(void *));
@@ -2645,59 +2550,92 @@ int v2e_emu_run(v2e_emu *h, const v2e_emu_params *p, const void *frames, int dty
     if (chain) {
         push(&h->ch_K, sizeof(h->ch_K)); push(&h->ch_E, sizeof(h->ch_E)); push(&h->ch_fused, sizeof(h->ch_fused)); push(&h->ch_nD, sizeof(h->ch_nD));
         push(&h->ch_max_blocks, sizeof(h->ch_max_blocks));
-        push(&h->ch_gM, sizeof(h->ch_gM)); push(&h->ch_tsold, sizeof(h->ch_tsold)); push(&h->ch_ck, sizeof(h->ch_ck)); push(&h->ch_cnt, sizeof(h->ch_cnt));
+        push(&r.ch_gM, sizeof(r.ch_gM)); push(&r.ch_tsold, sizeof(r.ch_tsold)); push(&h->ch_ck, sizeof(h->ch_ck)); push(&r.ch_cnt, sizeof(r.ch_cnt));
     }
-    auto get_exec = [&](int phase, hipGraphExec_t *out) -> int { // the cached graph of the run
-        std::vector<unsigned char> k2 = key;
-        k2.push_back((unsigned char)phase);
-        for (auto &cg : h->graphs)
-            if (cg.key == k2) { *out = cg.exec; cg.used = ++h->graph_clock; return 0; }
-        if (h->graphs.size() >= 24) { // drop the least recently used one (two scratch sets x the caller's buffer sets x the pieces of a run)
+    return key;
+}
+
+// V2E_RUN_GRAPH: the run's cached graph (captured on a miss, the least recently used one dropped beyond 24), launched on `s`
+static int run_graph(v2e_emu *h, const v2e_emu_params *p, const KArgs &a, const void *frames, int dtype, int n_frames, float *events,
+                     uint64_t cap, v2e_frame_rec *recs_dev, bool chain, hipStream_t s)
+{
+    std::vector<unsigned char> key = graph_key(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, chain);
+    hipGraphExec_t exec = nullptr;
+    for (auto &cg : h->graphs)
+        if (cg.key == key) { exec = cg.exec; cg.used = ++h->graph_clock; break; }
+    if (!exec) {
+        if (h->graphs.size() >= 24) { // (two scratch sets x the caller's buffer sets)
             size_t lru = 0;
             for (size_t i = 1; i < h->graphs.size(); ++i) if (h->graphs[i].used < h->graphs[lru].used) lru = i;
             hipGraphExecDestroy(h->graphs[lru].exec);
             h->graphs.erase(h->graphs.begin() + lru);
         }
         hipGraph_t g = nullptr;
-        int rc2 = 0;
-        if (legacy) { // one stream: plain stream capture
-            hipStream_t cs;
-            V2E_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-            V2E_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-            rc2 = enqueue_run(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, cs, nullptr);
-            hipError_t e = hipStreamEndCapture(cs, &g);
-            hipStreamDestroy(cs);
-            if (rc2) { if (g) hipGraphDestroy(g); return rc2; }
-            V2E_HIP(e);
-        } else if (getenv("V2E_AMD_GRAPH_EXPLICIT")) { // dev: the graph node by node (see Sched); this runtime then runs it serially
-            V2E_HIP(hipGraphCreate(&g, 0));
-            rc2 = enqueue_run_chain(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, s, g);
-            if (rc2) { hipGraphDestroy(g); return rc2; }
-        } else { // stream capture, with edges between the origin and the forked streams only
-            hipStream_t cs;
-            V2E_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-            V2E_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-            rc2 = enqueue_run_chain(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, cs, nullptr, nullptr, nullptr, true);
-            hipError_t e = hipStreamEndCapture(cs, &g);
-            hipStreamDestroy(cs);
-            if (rc2) { if (g) hipGraphDestroy(g); return rc2; }
-            V2E_HIP(e);
-        }
-        hipGraphExec_t exec = nullptr;
+        hipStream_t cs;
+        V2E_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+        V2E_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+        const int rc = chain ? enqueue_run_chain(h, p, a, dtype, n_frames, events, cap, recs_dev, cs, ChainMode::captured)
+                             : enqueue_run(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, cs);
+        hipError_t e = hipStreamEndCapture(cs, &g);
+        hipStreamDestroy(cs);
+        if (rc) { if (g) hipGraphDestroy(g); return rc; }
+        V2E_HIP(e);
         V2E_HIP(hipGraphInstantiate(&exec, g, nullptr, nullptr, 0));
         V2E_HIP(hipGraphDestroy(g));
-        h->graphs.push_back({k2, exec, ++h->graph_clock});
-        *out = exec;
-        return 0;
-    };
-    hipGraphExec_t exec = nullptr;
-    rc = get_exec(0, &exec);
-    if (rc) return rc;
+        h->graphs.push_back({std::move(key), exec, ++h->graph_clock});
+    }
     V2E_HIP(hipGraphLaunch(exec, s));
     return 0;
 }
 
-// host-blocking: every piece of the LAST overlapped run that used scratch set `ticket` (v2e_emu_run_ticket right after that run) is complete
+int v2e_emu_run(v2e_emu *h, const v2e_emu_params *p, const void *frames, int dtype, int n_frames, const double *t_prev,
+                const double *t_frame, uint32_t frame_idx0, float *events, uint64_t cap, v2e_frame_rec *recs_dev,
+                int flags, void *stream)
+{
+    int rc = check_params(h, p);
+    if (rc) return rc;
+    V2E_REQUIRE(p->rng_mode == V2E_RNG_PHILOX, "v2e_emu_run is the device-resident Philox path");
+    V2E_REQUIRE(frames && t_prev && t_frame && events && recs_dev && n_frames > 0, "bad run args");
+    V2E_REQUIRE(dtype == V2E_DT_U8 || dtype == V2E_DT_F32 || dtype == V2E_DT_F64, "bad frame dtype");
+    V2E_REQUIRE(!h->cs_sur || ((int)h->csr_steps.size() == n_frames && h->n_clips == 1),
+                "a run with a CSDVS surround needs v2e_emu_set_csdvs_run for exactly these frames (one clip)");
+    const bool chain_ok = chain_eligible(h, p, dtype);
+    V2E_REQUIRE(!(flags & V2E_RUN_REQUIRE_CHAIN) || chain_ok, "k_chain cannot run this configuration (max_iters, photoreceptor noise or float64 log frames)");
+    const bool chain = chain_ok && ((flags & V2E_RUN_REQUIRE_CHAIN) || !(flags & V2E_RUN_PER_FRAME_KERNELS));
+    const int mode = flags & 3; // 0 plain launches, V2E_RUN_GRAPH, V2E_RUN_PROFILE
+    const bool pipelined = (flags & V2E_RUN_PIPELINED) && mode == 0 && chain;
+    V2E_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (pipelined) h->scratch_par ^= 1; // (the other scratch set than the run before)
+    h->last_ticket = pipelined ? h->scratch_par : -1;
+    rc = reserve_run(h, n_frames, s);
+    if (rc) return rc;
+    if (chain) {
+        rc = chain_alloc(h, p, dtype, n_frames, flags, pipelined);
+        if (rc) return rc;
+    }
+    h->last_kind = chain ? (h->ch_fused ? 4 : 3) : 0;
+    h->last_fpl = chain ? h->ch_K : 1;
+    h->last_fpb = chain ? h->ch_E : 1;
+    const KArgs a = make_kargs(h, p);
+    if (pipelined)
+        return run_pipelined(h, p, a, frames, dtype, n_frames, t_prev, t_frame, frame_idx0, events, cap, recs_dev,
+                             (flags & V2E_RUN_FRAMES_RESIDENT) != 0, s);
+    if (h->join_runs(s)) { // every other run goes whole on the caller's stream, behind every piece still in flight
+        v2e_set_error("hipStreamWaitEvent failed");
+        return V2E_EHIP;
+    }
+    rc = upload_run(h, p, n_frames, t_prev, t_frame, frame_idx0, frames, s);
+    if (rc) return rc;
+    if (mode == V2E_RUN_PROFILE)
+        return chain ? run_profiled_chain(h, p, a, dtype, n_frames, events, cap, recs_dev, s)
+                     : run_profiled_frames(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, s);
+    if (mode != 0) return run_graph(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, chain, s);
+    return chain ? enqueue_run_chain(h, p, a, dtype, n_frames, events, cap, recs_dev, s, ChainMode::plain)
+                 : enqueue_run(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, s);
+}
+
+// host-blocking: every piece of the LAST pipelined run that used scratch set `ticket` (v2e_emu_run_ticket right after that run) is complete
 int v2e_emu_run_wait(v2e_emu *h, int ticket)
 {
     V2E_REQUIRE(h && (ticket == 0 || ticket == 1), "bad ticket");
@@ -2716,7 +2654,7 @@ const v2e_frame_rec *v2e_emu_run_recs(v2e_emu *h, int ticket, uint64_t *n_recs)
     return (const v2e_frame_rec *)h->recs_host[ticket];
 }
 
-// `stream` waits for every piece of every overlapped run (v2e_emu_run, |1024) enqueued on this handle so far
+// `stream` waits for every piece of every pipelined run (v2e_emu_run, V2E_RUN_PIPELINED) enqueued on this handle so far
 int v2e_emu_run_join(v2e_emu *h, void *stream)
 {
     V2E_REQUIRE(h, "null");
@@ -2789,11 +2727,11 @@ int v2e_emu_debug_chain_rows(v2e_emu *h, uint32_t *out, size_t cap_words, int *l
 {
     V2E_REQUIRE(h && launches && K, "null");
     *launches = h->ch_launch_cap; *K = h->ch_K;
-    if (!h->ch_gM || !out) return 0;
+    if (!h->cur().ch_gM || !out) return 0;
     V2E_HIP(hipSetDevice(h->device));
     V2E_HIP(hipDeviceSynchronize());
     const size_t n = (size_t)h->ch_launch_cap * (h->ch_K + 1) * h->n_clips * h->ch_K;
-    V2E_HIP(hipMemcpy(out, h->ch_gM, sizeof(uint32_t) * std::min(n, cap_words), hipMemcpyDeviceToHost));
+    V2E_HIP(hipMemcpy(out, h->cur().ch_gM, sizeof(uint32_t) * std::min(n, cap_words), hipMemcpyDeviceToHost));
     return 0;
 }
 

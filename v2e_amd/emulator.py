@@ -145,7 +145,7 @@ class _PendingRun:
     def __init__(self, emu, ev, recs, done, counts, start, return_device, empty, dts=None, ticket=None):
         self.emu, self.ev, self.recs, self._done = emu, ev, recs, done
         self.counts, self.start, self.return_device, self.empty, self.dts = counts, start, return_device, empty, dts
-        self.ticket = ticket  # overlapped runs (v2e_emu_run | 1024): what result() waits for on the host (v2e_emu_run_wait)
+        self.ticket = ticket  # pipelined runs (v2e_emu_run, RUN_PIPELINED): what result() waits for on the host (v2e_emu_run_wait)
         self._res = None
 
     @property
@@ -951,7 +951,7 @@ class EventEmulator(object):
         use_graph: True / 1 one hipGraph per run (what the blocking call uses: lowest latency of a single run), 0 plain launches.
         pipelined (default: on where use_graph is 0): consecutive runs overlap -- the run's upload and first records go out beside the run
         before, its last emission batches finish beside the run after, the current stream carries the chain's launches only
-        (v2e_emu_run, 0 | 1024): the throughput mode of a loop that keeps one run enqueued ahead (bench.py).  The current stream then
+        (v2e_emu_run, RUN_PIPELINED): the throughput mode of a loop that keeps one run enqueued ahead (bench.py).  The current stream then
         orders the pixel state only; result() waits for the rows.  frames_resident=True: the caller vouches that nothing enqueued on
         the current stream still writes `frames`; the run's head then need not wait for the chain of the run before.
         """
@@ -1012,10 +1012,6 @@ class EventEmulator(object):
                                      "amplitude was computed for inside this run; split the run there (or use generate_events "
                                      "per frame)")
             eng.set_pnoise(self._pn_plane, None)
-            if isinstance(use_graph, bool) or use_graph in (0, 1):
-                use_graph = int(use_graph) | 16  # the pipeline that carries the noise plane
-        if self.scidvs and (isinstance(use_graph, bool) or use_graph in (0, 1)):
-            use_graph = int(use_graph) | 16  # the kernels that carry the SCIDVS planes
         cs_steps_dev = None
         if self.csdvs_enabled:
             # emulator.py:1061-1124 inside the run: per frame the host part (step count, coefficients) as the reference computes
@@ -1038,8 +1034,6 @@ class EventEmulator(object):
             _capi.check(eng.lib.v2e_emu_set_csdvs_run(eng._h, scratch.data_ptr(), lp_new.data_ptr(), ap, ah, ns, nrun,
                                                       float(self.MAX_CHANGE_TO_TERMINATE_EULER_SURROUND_STEPPING),
                                                       cs_steps_dev.data_ptr()), "v2e_emu_set_csdvs_run")
-            if isinstance(use_graph, bool) or use_graph in (0, 1):
-                use_graph = int(use_graph) | 16  # the per-frame kernels carry the surround
         P = self._params()
         if cap is None:
             # 4 events per pixel and frame (the reference never drops events; a clip that exceeds this raises below and
@@ -1065,12 +1059,12 @@ class EventEmulator(object):
         recs = eng.alloc_recs(nrun, which)
         ug = int(use_graph)
         if getattr(self, "_refr_mostly_on", False):
-            ug |= 128  # one frame per launch: the speculating chain would redo most of its launches
-        if (ug & 3) == 0 and (pipelined or pipelined is None) and not _single_buffer:
-            ug |= 1024 | (2048 if frames_resident else 0)
+            ug |= _capi.RUN_ONE_FRAME_PER_LAUNCH  # the speculating chain would redo most of its launches
+        if (ug & (_capi.RUN_GRAPH | _capi.RUN_PROFILE)) == 0 and (pipelined or pipelined is None) and not _single_buffer:
+            ug |= _capi.RUN_PIPELINED | (_capi.RUN_FRAMES_RESIDENT if frames_resident else 0)
         eng.run(P, frames_dev[start:], t_prev, t_frames[start:], self.frame_counter, ev, recs, use_graph=ug)
         ticket = None
-        if ug & 1024:
+        if ug & _capi.RUN_PIPELINED:
             # the library may have enqueued the run in pieces on streams of its own: result() waits for them on the host; a device-side
             # event (the `done` property) is only built for a caller that asks for one
             done, ticket = None, eng.run_ticket()

@@ -326,7 +326,7 @@ class EmuEngine:
                 pool.release(buf)
 
     def run(self, P, frames_dev, t_prev, t_frame, frame_idx0, events, recs_dev, use_graph=True):
-        """Device-resident Philox run over frames_dev [F][n_clips][H*W]; no host sync."""
+        """Device-resident Philox run over frames_dev [F][n_clips][H*W]; no host sync.  use_graph: the v2e_emu_run flags (_capi.RUN_*)."""
         F = int(frames_dev.shape[0])
         self._check_frame(frames_dev, F * self.n_clips)
         tp = np.ascontiguousarray(np.asarray(t_prev, dtype=np.float64).reshape(F * self.n_clips))
@@ -338,7 +338,7 @@ class EmuEngine:
               "v2e_emu_run")
 
     def run_done_event(self):
-        """A torch event behind every piece of every overlapped run (use_graph | 1024) enqueued so far: recorded on a stream of the
+        """A torch event behind every piece of every pipelined run (use_graph | RUN_PIPELINED) enqueued so far: recorded on a stream of the
         engine that waits for them (v2e_emu_run_join), never on the caller's stream -- which carries the next run's chain."""
         js = self.__dict__.get("_join_stream")
         if js is None:
