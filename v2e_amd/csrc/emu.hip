@@ -803,7 +803,7 @@ struct RunScratch {
     // sized by the chain configuration (K, E, keys; v2e_emu::ch_*)
     uint32_t *ch_gM = nullptr;      // [ch_launch_cap][ch_K + 1][n_clips][ch_K]
     unsigned *ch_bar = nullptr;     // [ch_launch_cap][2 ch_K][n_clips]: one counter per rendezvous of a launch (passes + lock-step frames)
-    uint4 *ch_rec = nullptr;        // [ch_D][n_clips][npx_pad] k_ahead's per-(frame, pixel) records
+    uint2 *ch_rec = nullptr;        // [ch_D][n_clips][npx_pad] k_ahead's per-(frame, pixel) records (8 bytes: see AheadArgs)
     uint32_t *ch_cnt = nullptr;     // [ch_D][n_clips][npx_pad]
     uint32_t *ch_ruleM = nullptr;   // [ch_D][n_clips]
     float *ch_tsold = nullptr;      // [ch_D][n_clips][npx_pad] (refractory runs)
@@ -1742,14 +1742,14 @@ static bool chain_fused_records(const v2e_emu *h, int dtype, int nD)
 {
     if (dtype != V2E_DT_U8) return true; // k_ahead's record path is instantiated for uint8 frames only
     // k_chain reads k_ahead's records and writes the count words through buffer resources (32-bit offsets): the record ring of
-    // nD batches of up to 64 frames must stay below 4 GB (1280x720: 2.8 GB with three batches; beyond that the chain builds the records)
-    if ((size_t)nD * 64 * h->n_clips * h->npx_pad * sizeof(uint4) >= (1ull << 32)) return true;
+    // nD batches of up to 64 frames must stay below 4 GB (1280x720: 1.4 GB with three batches; beyond that the chain builds the records)
+    if ((size_t)nD * 64 * h->n_clips * h->npx_pad * sizeof(uint2) >= (1ull << 32)) return true;
     const char *fe = getenv("V2E_AMD_CHAIN_FUSED"); // read per call: tests switch it per emulator instance
     const int fused_env = fe ? atoi(fe) : -1;
     return fused_env >= 0 ? fused_env != 0 : !chain_small_grid(h);
 }
 
-static size_t chain_dyn_lds(bool fused) { return fused ? 0 : (size_t)CHAIN_SUB * BLOCK * sizeof(uint4); }
+static size_t chain_dyn_lds(bool fused) { return fused ? 0 : (size_t)CHAIN_SUB * BLOCK * sizeof(uint2); }
 
 // allon: every run-time feature switch of the frame loop is on (cutoff, leak, shot noise, refractory period: the v2e CLI
 // defaults) -> the instantiation without those tests; built for float64 state and uint8 frames (what that configuration has)
@@ -1864,7 +1864,7 @@ static int chain_alloc(v2e_emu *h, const v2e_emu_params *p, int dtype, int n_fra
     if (!chain_small_grid(h)) {
         if (h->ch_long_batches < 0) { // decided once per handle (the answer must not change with what the handle itself allocates)
             size_t free_b = 0, total_b = 0;
-            const size_t ring = (size_t)3 * 64 * h->n_clips * h->npx_pad * (sizeof(uint32_t) + sizeof(float) + sizeof(uint4));
+            const size_t ring = (size_t)3 * 64 * h->n_clips * h->npx_pad * (sizeof(uint32_t) + sizeof(float) + sizeof(uint2));
             h->ch_long_batches = (hipMemGetInfo(&free_b, &total_b) == hipSuccess && ring <= free_b / 8) ? 1 : 0;
         }
         // (64 clips of 346x260 have 2 048 (frame, clip) pairs in a 32-frame batch already: 11.64 Gev/s with 32 frames, 11.37 with 64)
@@ -1919,8 +1919,8 @@ static int chain_alloc(v2e_emu *h, const v2e_emu_params *p, int dtype, int n_fra
             V2E_HIP(hipMalloc(&r.ch_cpre16, 3 * sizeof(uint32_t) * E * nc * h->nkeys_cap * (h->ch_nwp / 16)));
         }
         if (!fused) { // (zero once: k_ahead never writes a slot's padding [npx, npx_pad), and k_chain's lanes beyond the frame read it)
-            V2E_HIP(hipMalloc(&r.ch_rec, sizeof(uint4) * (size_t)h->ch_D * nc * h->npx_pad));
-            V2E_HIP(hipMemset(r.ch_rec, 0, sizeof(uint4) * (size_t)h->ch_D * nc * h->npx_pad));
+            V2E_HIP(hipMalloc(&r.ch_rec, sizeof(uint2) * (size_t)h->ch_D * nc * h->npx_pad));
+            V2E_HIP(hipMemset(r.ch_rec, 0, sizeof(uint2) * (size_t)h->ch_D * nc * h->npx_pad));
         }
         // The fills above are ordered on the DEFAULT stream only, and a pipelined run's head (its k_ahead records, its tables) goes out on
         // streams of the handle that do not wait for it: enqueued behind a run still executing on the default stream, the record ring's

@@ -121,6 +121,14 @@ __device__ __forceinline__ TsGen frame_tsgen(const KArgs &a, const FrameCtl *c, 
 // launch that happens to run meanwhile.
 typedef float v2e_f4 __attribute__((ext_vector_type(4)));
 typedef unsigned int v2e_u4 __attribute__((ext_vector_type(4)));
+typedef unsigned int v2e_u2 __attribute__((ext_vector_type(2)));
+
+// value of lane `idx` (idx wave-uniform) of a float64 as a scalar
+__device__ __forceinline__ double lane_value_d(double v, int idx)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    return __longlong_as_double((long long)(((unsigned long long)lane_value((uint32_t)(u >> 32), idx) << 32) | lane_value((uint32_t)u, idx)));
+}
 __device__ __forceinline__ void store_event_wt(float4 *ev_clip, unsigned long long row, float t, float x, float y, float pol)
 {
     if (row < 0x7000000ull) { // byte offset below 2^31
@@ -145,7 +153,7 @@ struct ChainArgs {
     uint32_t *cnt;                    // [D][n_clips][npx_pad] count words, slot = frame % D
     uint32_t *ruleM;                  // [D][n_clips] M of a frame finalised by the refractory rule, 0 otherwise
     float *tsold;                     // [D][n_clips][npx_pad] ts_mem before a rule-on frame's update, or nullptr
-    const uint4 *rec;                 // [D][n_clips][npx_pad] k_ahead's per-(frame, pixel) records
+    const uint2 *rec;                 // [D][n_clips][npx_pad] k_ahead's per-(frame, pixel) records (8 bytes: see AheadArgs)
     uint32_t *gM_prev, *gM_cur;       // [K + 1][n_clips][K] rule-on maxima: row r = after r redo passes
     unsigned *bar_prev;               // [K][n_clips] rendezvous counters of the redo passes on the previous launch
     const void *base_in, *lp_in;      // state as the previous launch left it
@@ -178,15 +186,15 @@ struct ChainArgs {
 
 #define V2E_STAMP_C(i) do { if (V2E_CHAIN_STAMPS && ca.dbg && tid == 0) ca.dbg[(size_t)g * 16 + (i)] = wall_clock64(); } while (0)
 
-// One frame's state-independent quantities of a pixel as a 16-byte record (layout: see k_ahead):
-// lin-log / eps (emulator_utils.py:18-45, 80-96), leak step (:126-129, float32 left to right), shot decisions (:326-349).
+// One frame's state-independent quantities of a pixel as a 16-byte record (layout: see k_ahead), in two parts: the table part
+// (lin-log / eps, emulator_utils.py:18-45, 80-96) is a function of the pixel value and the frame's dt_over_tau alone; the random
+// part (leak step, :126-129, float32 left to right; shot decisions, :326-349) needs the Philox draws.  k_ahead computes the random
+// part and stores it with the pixel byte (8 bytes), k_chain rebuilds the table part from them with the same expressions.
 template <typename FT>
-__device__ __forceinline__ uint4 make_frame_record(const KArgs &a, FT px, const float *s_lutL, const double *s_lutI, double dt_over_tau,
-                                                   double shot_base, float dtime_f, float lk, float thp, float ppre, float npre, float rr,
-                                                   float uu)
+__device__ __forceinline__ void frame_record_table(const KArgs &a, FT px, const float *s_lutL, const double *s_lutI, double dt_over_tau,
+                                                   double &L, double &inten01, double &eps)
 {
     constexpr bool U8 = sizeof(FT) == 1;
-    double L, inten01;
     if (U8) {
         L = a.log_input ? (double)px : (double)s_lutL[(int)px];
         inten01 = s_lutI[(int)px];
@@ -195,39 +203,74 @@ __device__ __forceinline__ uint4 make_frame_record(const KArgs &a, FT px, const 
         L = a.log_input ? x : (double)lin_log(x);
         inten01 = a.use_inten ? (x + 20.0) / 275.0 : 0.0;
     }
-    double eps = 0.0;
+    eps = 0.0;
     if (a.has_cutoff) {
         eps = inten01 * dt_over_tau;
         if (eps > 1.0) eps = 1.0;
     }
-    float dl = 0.f;
+}
+
+// the random part: the leak step and the shot decisions (bit 0 ON, bit 1 OFF)
+__device__ __forceinline__ void frame_record_rand(const KArgs &a, double inten01, double shot_base, float dtime_f, float lk, float thp,
+                                                  float ppre, float npre, float rr, float uu, float &dl, uint32_t &sb)
+{
+    dl = 0.f;
     if (a.do_leak) {
         const float rate = lk * (1.0f - a.jit_f * rr);
         dl = (dtime_f * rate) * thp;
     }
-    uint32_t sb = 0;
+    sb = 0;
     if (a.do_shot) {
         const double F = shot_base * (a.inten_slope * inten01 + 1);
         if ((double)uu > 1 - F * (double)ppre) sb |= 1u; // ON -> bit 30 of the high word
         if ((double)uu < F * (double)npre) sb |= 2u;     // OFF -> bit 31
     }
+}
+
+__device__ __forceinline__ uint4 pack_frame_record(double eps, double L, uint32_t dl_bits, uint32_t sb)
+{
     const unsigned long long eb = (unsigned long long)__double_as_longlong(eps);
     uint4 r;
     r.x = (uint32_t)eb;
     r.y = (uint32_t)(eb >> 32) | (sb << 30);
     r.z = __float_as_uint((float)L);
-    r.w = __float_as_uint(dl);
+    r.w = dl_bits;
     return r;
+}
+
+template <typename FT>
+__device__ __forceinline__ uint4 make_frame_record(const KArgs &a, FT px, const float *s_lutL, const double *s_lutI, double dt_over_tau,
+                                                   double shot_base, float dtime_f, float lk, float thp, float ppre, float npre, float rr,
+                                                   float uu)
+{
+    double L, inten01, eps;
+    frame_record_table<FT>(a, px, s_lutL, s_lutI, dt_over_tau, L, inten01, eps);
+    float dl;
+    uint32_t sb;
+    frame_record_rand(a, inten01, shot_base, dtime_f, lk, thp, ppre, npre, rr, uu, dl, sb);
+    return pack_frame_record(eps, L, __float_as_uint(dl), sb);
+}
+
+// k_ahead's 8-byte record (see AheadArgs) of a uint8 frame -> the 16-byte record, with the frame's dt_over_tau
+__device__ __forceinline__ uint4 decode_frame_record(const KArgs &a, uint2 r8, const float *s_lutL, const double *s_lutI, double dt_over_tau)
+{
+    double L, inten01, eps;
+    frame_record_table<uint8_t>(a, (uint8_t)(r8.y & 0xFFu), s_lutL, s_lutI, dt_over_tau, L, inten01, eps);
+    return pack_frame_record(eps, L, r8.x, r8.y >> 30);
 }
 
 // Everything about a frame that depends on no state, for all frames of a chain launch at once: lin-log of the pixel,
 // the low-pass coefficient eps (emulator_utils.py:80-96), the Philox draws, the leak step delta_leak
 // (emulator_utils.py:126-129, float32 left to right) and the shot-noise decisions (emulator_utils.py:326-349).  One thread per
 // (pixel, frame pair), so the draws of a pair cost one Philox call and the work runs at full occupancy beside the chain
-// instead of inside its one-wave-per-SIMD dependency chain.  Result: one 16-byte record per (frame, pixel)
+// instead of inside its one-wave-per-SIMD dependency chain.  Result: one 8-byte record per (frame, pixel) of uint8 frames
+//   .x     delta_leak (float32)
+//   .y     the pixel byte (bits 0-7), the shot ON / OFF decisions (bits 30, 31)
+// from which k_chain rebuilds, with the frame's dt_over_tau, the 16-byte record frame_body reads (make_frame_record)
 //   .x .y  eps (float64, in [0,1]: top exponent bit and sign bit are free and carry the shot ON / OFF decisions)
 //   .z     lin-log value L (float32; the frame itself when it is log-encoded already)
 //   .w     delta_leak (float32)
+// (the table part -- L and eps -- is a function of the pixel byte and a per-frame scalar: storing it would double the ring's traffic)
 struct AheadArgs {
     const void *const *frames_pp; // *frames_pp = frames of the run (see ChainArgs)
     unsigned long long frame_stride;
@@ -236,20 +279,16 @@ struct AheadArgs {
     int f0, nf, D, n_clips;
     int slot0;  // f0 % D, from the host (a 64-bit remainder per frame and thread is ~60 instructions of a kernel that has 240)
     int ppt;    // frame pairs per thread (grid z = ceil(pairs / ppt))
-    uint4 *rec; // [D][n_clips][npx_pad]
+    uint2 *rec; // [D][n_clips][npx_pad]
 };
 
 template <typename FT>
 __global__ __launch_bounds__(BLOCK) void k_ahead(KArgs a, AheadArgs aa)
 {
-    __shared__ float s_lutL[256];
+    static_assert(sizeof(FT) == 1, "k_ahead's records carry the pixel byte: uint8 frames only");
     __shared__ double s_lutI[256];
-    constexpr bool U8 = sizeof(FT) == 1;
     const int tid = threadIdx.x;
-    if (U8) {
-        s_lutL[tid] = a.lut_L[tid];
-        s_lutI[tid] = a.lut_I[tid];
-    }
+    s_lutI[tid] = a.lut_I[tid];
     __syncthreads();
     const int clip = blockIdx.y, p = blockIdx.x * BLOCK + tid;
     if (p >= a.npx) return;
@@ -281,9 +320,12 @@ __global__ __launch_bounds__(BLOCK) void k_ahead(KArgs a, AheadArgs aa)
             //  64-bit products of uniform values are four scalar instructions each)
             const FrameCtl *c = aa.ctl + (f * aa.n_clips + clip);
             const FT px = ((const FT *)(frames + (size_t)f * aa.frame_stride))[(size_t)clip * a.npx + p];
-            const uint4 r = make_frame_record<FT>(a, px, s_lutL, s_lutI, c->dt_over_tau, c->shot_base, (float)(c->t_frame - c->t_prev), lk, thp,
-                                                  ppre, npre, half ? r_even : r_odd, half ? u_even : u_odd);
-            aa.rec[((uint32_t)sl * (uint32_t)aa.n_clips + (uint32_t)clip) * (uint32_t)a.npx_pad + (uint32_t)p] = r;
+            float dl;
+            uint32_t sb;
+            frame_record_rand(a, s_lutI[px], c->shot_base, (float)(c->t_frame - c->t_prev), lk, thp, ppre, npre, half ? r_even : r_odd,
+                              half ? u_even : u_odd, dl, sb);
+            aa.rec[((uint32_t)sl * (uint32_t)aa.n_clips + (uint32_t)clip) * (uint32_t)a.npx_pad + (uint32_t)p] =
+                make_uint2(__float_as_uint(dl), (uint32_t)px | (sb << 30));
         }
     }
 }
@@ -307,8 +349,9 @@ template <typename R> __device__ __forceinline__ R floor_div_rcp(R a, R b, R rb)
 
 // FUSED = false: the frames' records come from k_ahead through LDS (small grids: the chain is one wave per SIMD and every
 // instruction in it is latency).  FUSED = true: the chain builds each record itself (large grids: the occupancy hides
-// latencies, and the records' 32 B per pixel and frame of extra HBM traffic would be what bounds the run).
-// Dynamic LDS (FUSED = false): [CHAIN_SUB][BLOCK] uint4 records.
+// latencies, and the records' 16 B per pixel and frame of extra HBM traffic -- 8 written, 8 read back -- would be what bounds the run).
+// Dynamic LDS (FUSED = false): [CHAIN_SUB][BLOCK] k_ahead's 8-byte records; frame_body rebuilds the 16-byte record from one with two
+// LDS table reads and a float64 multiply that no pixel state feeds.
 // ALLON: instantiation for runs with a photoreceptor cutoff, leak, shot noise AND a refractory period (the v2e CLI defaults,
 // i.e. the benchmark): the per-frame tests of those run-time switches -- a scalar compare and a branch each, in a loop whose
 // every instruction is exposed latency -- are compiled out.  ALLON = false reads the switches from KArgs.
@@ -321,9 +364,9 @@ void k_chain(KArgs a_in, ChainArgs ca)
 {
     KArgs a = a_in;
     if (ALLON) { a.has_cutoff = 1; a.do_leak = 1; a.do_shot = 1; a.has_refr = 1; a.use_inten = 1; }
-    extern __shared__ uint4 s_arec[];         // [CHAIN_SUB][BLOCK] k_ahead's records of the frames in flight
-    __shared__ float s_lutL[FUSED ? 256 : 1]; // FUSED: lin-log tables and the pass's frame scalars
-    __shared__ double s_lutI[FUSED ? 256 : 1];
+    extern __shared__ uint2 s_arec[];         // [CHAIN_SUB][BLOCK] k_ahead's records of the frames in flight
+    __shared__ float s_lutL[256];             // lin-log tables: FUSED builds its records with them, !FUSED decodes k_ahead's
+    __shared__ double s_lutI[256];            // FUSED: and the pass's frame scalars
     __shared__ double s_dtau[FUSED ? CHAIN_K_MAX : 1], s_shot[FUSED ? CHAIN_K_MAX : 1];
     __shared__ float s_dtime[FUSED ? CHAIN_K_MAX : 1];
     constexpr bool U8 = sizeof(FT) == 1;
@@ -339,6 +382,12 @@ void k_chain(KArgs a_in, ChainArgs ca)
     if (stamp && tid == 0) atomicMax(stamp + 2 * ca.lidx, ~wall_clock64());
     uint32_t fbase = 0u;
     const char *frames = nullptr;
+    float tab_L = 0.f; // !FUSED: this thread's entry of the lin-log tables, to LDS behind the prologue's wait
+    double tab_I = 0.0;
+    if (!FUSED) {
+        tab_L = a.lut_L[tid];
+        tab_I = a.lut_I[tid];
+    }
     if (FUSED) {
         fbase = *ca.fidx_base;
         frames = (const char *)*ca.frames_pp;
@@ -367,19 +416,25 @@ void k_chain(KArgs a_in, ChainArgs ca)
         const uint32_t slot_px = (uint32_t)((size_t)ca.n_clips * a.npx_pad); // pixels of one ring slot
         const __amdgpu_buffer_rsrc_t rec_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)ca.rec, 0, -1, 0x00020000);
         const __amdgpu_buffer_rsrc_t cnt_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)ca.cnt, 0, -1, 0x00020000);
-        auto load_rec = [&](const int sl) __attribute__((always_inline)) -> uint4 {
-            const v2e_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rec_rsrc, (int)(lane_px * 16u), (int)((uint32_t)sl * slot_px * 16u), 0);
-            return make_uint4(v.x, v.y, v.z, v.w);
+        auto load_rec = [&](const int sl) __attribute__((always_inline)) -> uint2 {
+            const v2e_u2 v = __builtin_amdgcn_raw_buffer_load_b64(rec_rsrc, (int)(lane_px * 8u), (int)((uint32_t)sl * slot_px * 8u), 0);
+            return make_uint2(v.x, v.y);
+        };
+        // the 16-byte record of frame k of a pass from k_ahead's 8-byte one, with the frame's dt_over_tau (dtau_v: lane k = frame k of the
+        // pass) -- and a ZERO record for a lane beyond the frame: with its zero state it gives no events (the frame loop carries no
+        // per-lane validity test; a zero 8-byte record does not decode to zero: lut_I[0] > 0)
+        auto decode_rec = [&](const uint2 r8, const double dtau_v, const int k) __attribute__((always_inline)) -> uint4 {
+            const double dtau = a.has_cutoff ? lane_value_d(dtau_v, k) : 0.0;
+            const uint4 r = decode_frame_record(a, r8, s_lutL, s_lutI, dtau);
+            return valid ? r : make_uint4(0u, 0u, 0u, 0u);
         };
         auto stage = [&](const int sl0, const int fn) __attribute__((always_inline)) { // the first CHAIN_SUB frames of a pass (sl0: the first one's slot)
             if (FUSED) return;
-            // (a lane beyond the frame stages ZERO records: with its zero state they give no events -- the frame loop carries no
-            // per-lane validity test)
-            uint4 t[CHAIN_SUB];
+            uint2 t[CHAIN_SUB];
             int sl = sl0;
 #pragma unroll
             for (int j = 0; j < CHAIN_SUB; ++j) {
-                t[j] = make_uint4(0u, 0u, 0u, 0u);
+                t[j] = make_uint2(0u, 0u);
                 if (j < fn && valid) t[j] = load_rec(sl);
                 if (++sl == ca.D) sl = 0;
             }
@@ -421,6 +476,13 @@ void k_chain(KArgs a_in, ChainArgs ca)
             if (lane < ca.nf) mon_own = ca.ctl[(size_t)(ca.f0 + lane) * ca.n_clips + clip].refr_on_n;
             if (!own && lane < ca.pnf) mon_prev = ca.ctl[(size_t)(ca.pf0 + lane) * ca.n_clips + clip].refr_on_n;
         }
+        // !FUSED, lane k of every wave: dt_over_tau of frame k of this launch / of the previous one (a redo pass decodes the previous
+        // launch's records with ITS frames' scalars)
+        double dtau_own = 0.0, dtau_prev = 0.0;
+        if (!FUSED && a.has_cutoff) {
+            if (lane < ca.nf) dtau_own = ca.ctl[(size_t)(ca.f0 + lane) * ca.n_clips + clip].dt_over_tau;
+            if (!own && lane < ca.pnf) dtau_prev = ca.ctl[(size_t)(ca.pf0 + lane) * ca.n_clips + clip].dt_over_tau;
+        }
         double dtau_r = 0.0, shot_r = 0.0;
         float dtime_r = 0.f, nr = 0.f;
         if (FUSED && tid < ca.nf) {
@@ -431,7 +493,16 @@ void k_chain(KArgs a_in, ChainArgs ca)
         }
         if (FUSED && valid && a.do_leak) nr = a.noise_rate[sp];
         stage(ca.slot_f0, ca.nf); // this launch's own frames (almost always the only pass)
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(b), "+v"(lp), "+v"(tsm), "+v"(thp), "+v"(thn), "+v"(gM_v), "+v"(mon_own), "+v"(mon_prev) : : "memory");
+        if (FUSED)
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(b), "+v"(lp), "+v"(tsm), "+v"(thp), "+v"(thn), "+v"(gM_v), "+v"(mon_own), "+v"(mon_prev) : : "memory");
+        else
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(b), "+v"(lp), "+v"(tsm), "+v"(thp), "+v"(thn), "+v"(gM_v), "+v"(mon_own), "+v"(mon_prev),
+                         "+v"(dtau_own), "+v"(dtau_prev), "+v"(tab_L), "+v"(tab_I) : : "memory");
+        if (!FUSED && clip == (int)blockIdx.y) { // (the tables stay in LDS for the workgroup's later clips)
+            s_lutL[tid] = tab_L;
+            s_lutI[tid] = tab_I;
+            __syncthreads();
+        }
         if (FUSED) {
             if (tid < CHAIN_K_MAX) {
                 s_dtau[tid] = dtau_r;
@@ -509,6 +580,7 @@ void k_chain(KArgs a_in, ChainArgs ca)
             if (own) { fs = ca.f0; fn = ca.nf; gM_dst = ca.gM_cur + (size_t)clip * ca.K; c0 = 0; }
             else { fs = ca.pf0; fn = ca.pnf; gM_dst = ca.gM_prev + ((size_t)round * ca.n_clips + clip) * ca.K; }
             const int fs_slot = own ? ca.slot_f0 : ca.slot_pf0;
+            const double dtau_v = own ? dtau_own : dtau_prev;
             if (redone) { // a redo pass, or the own pass after one: its inputs replace what the prologue staged
                 fill_scalars(fs, fn);
                 stage(wrap_slot(fs_slot + c0), fn - c0);
@@ -548,7 +620,9 @@ void k_chain(KArgs a_in, ChainArgs ca)
                     rc = make_frame_record<FT>(a, px, s_lutL, s_lutI, s_dtau[k], s_shot[k], s_dtime[k], lk, thp, ppre, npre,
                                                even ? r_even : r_odd, even ? u_even : u_odd);
                 } else {
-                    rc = s_arec[(size_t)js * BLOCK + tid];
+                    // (decoded here, not where the boundary stages it: no pixel state feeds it, and the boundary stays a copy --
+                    //  profiles/r07_emulator_experiments.txt item 2)
+                    rc = decode_rec(s_arec[(size_t)js * BLOCK + tid], dtau_v, k);
                 }
                 const double eps = __longlong_as_double((long long)(((unsigned long long)(rc.y & 0x3FFFFFFFu) << 32) | rc.x));
                 const double L = (double)__uint_as_float(rc.z);
@@ -644,13 +718,15 @@ void k_chain(KArgs a_in, ChainArgs ca)
                 return cw;
             };
             // records of the pass's frames [kn, kn + CHAIN_SUB) into registers (in flight while the frames before them compute)
-            uint4 nx[CHAIN_SUB];
+            // (two sub-passes ahead instead of one -- the registers the 8-byte records freed -- measured slower:
+            //  profiles/r07_emulator_experiments.txt item 3)
+            uint2 nx[CHAIN_SUB];
             auto fetch_next = [&](const int kn) __attribute__((always_inline)) {
                 const int cn = min(CHAIN_SUB, fn - kn); // <= 0: none
                 int sl = cn > 0 ? wrap_slot(fs_slot + kn) : 0;
 #pragma unroll
                 for (int j = 0; j < CHAIN_SUB; ++j) {
-                    nx[j] = make_uint4(0u, 0u, 0u, 0u);
+                    nx[j] = make_uint2(0u, 0u);
                     if (!FUSED && valid && j < cn) nx[j] = load_rec(sl);
                     if (++sl == ca.D) sl = 0;
                 }
