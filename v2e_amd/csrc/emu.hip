@@ -757,6 +757,12 @@ __global__ __launch_bounds__(256) void k_frame_rows_to_host(const float4 *__rest
 }
 
 #include "emu_chain.h"
+// k_cpull<false>: pixels' worth of a frame's rows per workgroup (wpf = npx / this; 346x260: 5 workgroups per frame).  Round 8
+// (pixels per workgroup, rows per thread): (2048, 2) / (4096, 2) / (8192, 4) / (16384, 8) measured about 0.566 / 0.558 / 0.556 /
+// 0.548 ms per headline step, the parent 0.575 (profiles/r08_emulator_experiments.txt).
+#ifndef V2E_PULL_PX_PER_WG
+#define V2E_PULL_PX_PER_WG 16384
+#endif
 
 } // namespace
 
@@ -2062,13 +2068,13 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
         ea.cdone = r.ch_cdone + set;
         const bool pull = r.ch_cmask != nullptr;
         ea.cmask = pull ? r.ch_cmask + set * h->ch_nwp * h->nkeys_cap * 2 * GPX : nullptr;
-        // k_cpull: small frames search a whole prefix row in LDS (346x260: 1.4 KB per key), a workgroup per ~2048 pixels' worth of
-        // a frame's rows; large ones search every 16th entry there and one line from L2, and take more, smaller workgroups (their
+        // k_cpull: small frames search a whole prefix row in LDS (346x260: 1.4 KB per key) through a bucket index, a workgroup per
+        // V2E_PULL_PX_PER_WG pixels' worth of a frame's rows; large ones search every 16th entry there and one line from L2, and take more, smaller workgroups (their
         // batches are few frames: the launch needs the parallelism)
         bool two = h->ch_nwp > 1024;
         if (const char *ev = getenv("V2E_AMD_PULL_TWO_LEVEL")) two = atoi(ev) != 0;
         ea.cpre16 = pull && two ? r.ch_cpre16 + set * h->nkeys_cap * (h->ch_nwp / 16) : nullptr;
-        ea.wpf = std::max(4, std::min(two ? 128 : 64, h->npx / 2048)); // (1280x720 noisy, round 5: 450 workgroups per frame 9.28, 128: 9.68, push 9.41 Gev/s)
+        ea.wpf = std::max(4, std::min(two ? 128 : 64, h->npx / (two ? 2048 : V2E_PULL_PX_PER_WG))); // (1280x720 noisy, round 5: 450 workgroups per frame 9.28, 128: 9.68, push 9.41 Gev/s)
         ea.p2 = two ? 16 : 64;
         while (ea.p2 < (two ? h->ch_nwp / 16 : ea.nwaves)) ea.p2 *= 2;
         ea.events = (float4 *)events; ea.cap = cap;
@@ -2109,7 +2115,7 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
         if (!captured && sc.wait(row_stream, EV_TAB, b)) return V2E_EHIP;
         if (mark(true, sc.st[row_stream])) return V2E_EHIP;
         if (pull) {
-            if (sc.kernel(row_stream, ea.cpre16 ? (const void *)k_cpull<true> : (const void *)k_cpull<false>, dim3(8 * ea.wpf * ((ea.nE + 7) / 8), NC), dim3(BLOCK), (size_t)(2 * ea.p2 * 4), args)) return V2E_EHIP;
+            if (sc.kernel(row_stream, ea.cpre16 ? (const void *)k_cpull<true> : (const void *)k_cpull<false>, dim3(8 * ea.wpf * ((ea.nE + 7) / 8), NC), dim3(BLOCK), (size_t)(2 * ea.p2 * (ea.cpre16 ? 4 : 6)), args)) return V2E_EHIP;
         } else if (sc.kernel(row_stream, (const void *)k_cemit, dim3(egx, NC, ea.nE), dim3(BLOCK), (size_t)REC_LDS, args)) return V2E_EHIP;
         if (mark(true, sc.st[row_stream])) return V2E_EHIP;
         return sc.record(EV_JOIN, b, row_stream);

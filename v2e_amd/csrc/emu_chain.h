@@ -31,6 +31,7 @@
 //
 //   Clips (independent pixel arrays) beyond what is co-resident are walked by a loop inside the workgroup.
 #pragma once
+#include "pull_index.h"
 
 // lock-step frames in redo passes (see k_chain): measured round 4, break-even at best; compiled out by default (the per-frame
 // test costs the common path), -DV2E_CHAIN_LOCKSTEP=1 + V2E_AMD_LOCKSTEP=1 bring it back
@@ -934,6 +935,22 @@ __global__ __launch_bounds__(BLOCK) void k_ctot(KArgs a, CEmitArgs ea)
             }
             if (lane < 4 * GPX) mrow[(size_t)key_on * ea.nwp * (2 * GPX)] = mw;
         };
+        // Per iteration the ON and OFF words are the ballot of the iteration's pixels, split by polarity.  The split and the
+        // totals are done on the VALU, not the scalar unit (which the chain shares, one per CU): the ballot's words go to lanes
+        // 0 .. 2 GPX - 1 and, by DPP, to the next 2 GPX, each lane keeps the bits of its polarity (pmask), and the ON / OFF totals
+        // are the sums of the words' popcounts over those lanes (a row_shr scan: lane 2 GPX - 1 and 4 GPX - 1).
+        static_assert(4 * GPX == 16, "k_ctot: the mask words of an iteration are one 16-lane DPP row");
+        uint32_t pmask = 0u;
+        if (mrow) {
+#pragma unroll
+            for (int j = 0; j < GPX; ++j) {
+                asm("v_writelane_b32 %0, %1, %2" : "+v"(pmask) : "s"((uint32_t)negb[j]), "n"(2 * j));
+                asm("v_writelane_b32 %0, %1, %2" : "+v"(pmask) : "s"((uint32_t)(negb[j] >> 32)), "n"(2 * j + 1));
+                asm("v_writelane_b32 %0, %1, %2" : "+v"(pmask) : "s"((uint32_t)negb[j]), "n"(2 * GPX + 2 * j));
+                asm("v_writelane_b32 %0, %1, %2" : "+v"(pmask) : "s"((uint32_t)(negb[j] >> 32)), "n"(2 * GPX + 2 * j + 1));
+            }
+            pmask = lane < 2 * GPX ? ~pmask : (lane < 4 * GPX ? pmask : 0u);
+        }
         const int wmc = min(wm, a.max_iters); // beyond max_iters the frame is flagged and not emitted
         const int nkw = 2 + 2 * wmc;
         bool ruled = false;
@@ -955,16 +972,12 @@ __global__ __launch_bounds__(BLOCK) void k_ctot(KArgs a, CEmitArgs ea)
             uint32_t mine = 0;
             const int i_lo = kb == 0 ? 0 : (kb - 2) / 2;
             const int i_hi = min((kb + WAVE - 2) / 2, wmc);
+            uint32_t *mrow_i = mrow ? mrow + (size_t)(2 + 2 * i_lo) * ea.nwp * (2 * GPX) : nullptr; // iteration i's ON key row
             for (int i = i_lo; i < i_hi; ++i) {
-                uint32_t on = 0, off = 0;
-                unsigned long long on_m[GPX], off_m[GPX];
-                if (!ruled) { // the common case: one compare per sub-group, the polarity split on the scalar unit
+                unsigned long long cb[GPX]; // the sub-groups' pixels with an event of iteration i (either polarity)
+                if (!ruled) { // the common case: one compare per sub-group
 #pragma unroll
-                    for (int j = 0; j < GPX; ++j) {
-                        const unsigned long long cb = __ballot(magv[j] > i);
-                        on_m[j] = cb & ~negb[j];
-                        off_m[j] = cb & negb[j];
-                    }
+                    for (int j = 0; j < GPX; ++j) cb[j] = __ballot(magv[j] > i);
                 } else {
 #pragma unroll
                     for (int j = 0; j < GPX; ++j) {
@@ -975,16 +988,36 @@ __global__ __launch_bounds__(BLOCK) void k_ctot(KArgs a, CEmitArgs ea)
                             pass = pt > a.refr_f;
                             if (pass) tsm[j] = t;
                         }
-                        on_m[j] = __ballot(pass && !neg[j]);
-                        off_m[j] = __ballot(pass && neg[j]);
+                        cb[j] = __ballot(pass);
                     }
                 }
+                uint32_t on, off;
+                if (mrow) {
+                    uint32_t mw = 0u;
 #pragma unroll
-                for (int j = 0; j < GPX; ++j) {
-                    on += (uint32_t)__popcll(on_m[j]);
-                    off += (uint32_t)__popcll(off_m[j]);
+                    for (int j = 0; j < GPX; ++j) {
+                        asm("v_writelane_b32 %0, %1, %2" : "+v"(mw) : "s"((uint32_t)cb[j]), "n"(2 * j));
+                        asm("v_writelane_b32 %0, %1, %2" : "+v"(mw) : "s"((uint32_t)(cb[j] >> 32)), "n"(2 * j + 1));
+                    }
+                    // lanes 2 GPX .. 4 GPX - 1 <- lanes 0 .. 2 GPX - 1 (row_shr:8 into banks 2 and 3 of the row; banks 0 and 1 keep theirs)
+                    mw = (uint32_t)__builtin_amdgcn_update_dpp((int)mw, (int)mw, 0x118, 0xf, 0xc, false) & pmask;
+                    if (lane < 4 * GPX) *mrow_i = mw;
+                    mrow_i += (size_t)2 * ea.nwp * (2 * GPX);
+                    int c = __popc(mw);
+                    c += V2E_DPP(c, 0x111); // row_shr:1
+                    c += V2E_DPP(c, 0x112); // row_shr:2
+                    c += V2E_DPP(c, 0x114); // row_shr:4 -- lane 2 GPX - 1: lanes 0 .. 2 GPX - 1, lane 4 GPX - 1: the next 2 GPX
+                    on = (uint32_t)__builtin_amdgcn_readlane(c, 2 * GPX - 1);
+                    off = (uint32_t)__builtin_amdgcn_readlane(c, 4 * GPX - 1);
+                } else {
+                    on = 0u;
+                    off = 0u;
+#pragma unroll
+                    for (int j = 0; j < GPX; ++j) {
+                        on += (uint32_t)__popcll(cb[j] & ~negb[j]);
+                        off += (uint32_t)__popcll(cb[j] & negb[j]);
+                    }
                 }
-                if (mrow) put_masks(2 + 2 * i, on_m, off_m);
                 const int kl = 2 + 2 * i - kb;
                 if (lane == kl) mine = on;
                 if (lane == kl + 1) mine = off;
@@ -1510,11 +1543,23 @@ __global__ __launch_bounds__(BLOCK) void k_cemit(KArgs a, CEmitArgs ea)
 // one frame share blockIdx.x mod 8, i.e. an XCD and its L2 (prefix rows and masks of the frame are read from HBM once).
 static_assert(GPX == 4, "k_cpull selects a pixel of a 256-pixel group (v2e_nth_set_bit_256)");
 // TWO (large frames: a prefix row of 1280x720 is 14 KB): two levels -- every 16th entry in LDS, then the 16 entries (one line,
-// from L2) searched in registers.
+// from L2) searched in registers.  !TWO: the whole row in LDS and a bucket index over it (pull_index.h, round 8): one index read and
+// a search over the couple of groups it leaves, instead of log2(p2) dependent reads.
+// Rows per thread and trip (round 8, interleaved A/B at 346x260 in profiles/r08_emulator_experiments.txt): 8 on the single level
+// (114 VGPRs, 4 waves per SIMD, with 16384 pixels' worth of rows per workgroup: fewer, fuller workgroups beside the chain), 4 on
+// the two-level path, where 8 cost the 1280x720 leg 3 % (its search holds a line of 16 entries per row in registers).
+#ifndef V2E_PULL_ROWS
+#define V2E_PULL_ROWS 8
+#endif
+#ifndef V2E_PULL_ROWS_TWO
+#define V2E_PULL_ROWS_TWO 4
+#endif
 template <bool TWO>
 __global__ __launch_bounds__(BLOCK) void k_cpull(KArgs a, CEmitArgs ea)
 {
+    constexpr int PULL_ROWS = TWO ? V2E_PULL_ROWS_TWO : V2E_PULL_ROWS;
     extern __shared__ uint32_t s_pre[]; // [2][p2]: the ON and the OFF key's prefix row (TWO: its coarse level) of the iteration at hand
+    uint16_t *const s_idx = (uint16_t *)(s_pre + 2 * ea.p2); // !TWO: [2][p2] the rows' bucket indices (pull_index.h)
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int clip = blockIdx.y;
     const int blk = (int)blockIdx.x >> 3;
@@ -1568,6 +1613,7 @@ __global__ __launch_bounds__(BLOCK) void k_cpull(KArgs a, CEmitArgs ea)
         const uint32_t T_on = cT[key0], T_off = cT[key0 + 1];
         const uint32_t r_lo = max(lo, base), r_hi = min(hi, base + T_on + T_off);
         if (r_lo >= r_hi) continue; // (uniform: none of this iteration's rows in the workgroup's range)
+        const uint32_t sh_on = pull_bucket_shift(T_on, (uint32_t)P2), sh_off = pull_bucket_shift(T_off, (uint32_t)P2);
         if (staged) __syncthreads(); // the readers of the rows staged before
         if (TWO) {
             const int nc16 = ea.nwp / 16;
@@ -1576,12 +1622,22 @@ __global__ __launch_bounds__(BLOCK) void k_cpull(KArgs a, CEmitArgs ea)
                 const int kk = k & (P2 - 1);
                 s_pre[k] = kk < nc16 ? pre16[(size_t)(k >= P2 ? nc16 : 0) + kk] : 0xFFFFFFFFu;
             }
-        } else { // four entries per load (nwp is a multiple of 16; entries nwaves .. nwp - 1 hold the key's total: never <= cp)
+        } else { // four entries per load (nwp is a multiple of 16; entries nwaves .. nwp - 1 hold the key's total: never <= cp),
+                 // and the bucket index entries those four groups hold (pull_index.h), from the four and the entry after them
             for (int k = tid * 4; k < 2 * P2; k += BLOCK * 4) {
-                const int kk = k & (P2 - 1);
+                const int kk = k & (P2 - 1), h = k >= P2 ? 1 : 0;
+                const uint32_t *src = pre + (size_t)(key0 + h) * ea.nwp;
                 uint4 v = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-                if (kk < ea.nwp) v = *(const uint4 *)(pre + (size_t)(key0 + (k >= P2 ? 1 : 0)) * ea.nwp + kk);
+                uint32_t nx = 0xFFFFFFFFu;
+                if (kk < ea.nwp) v = *(const uint4 *)(src + kk);
+                if (kk + 4 < ea.nwp) nx = src[kk + 4];
                 *(uint4 *)(s_pre + k) = v;
+                const uint32_t T = h ? T_off : T_on, sh = h ? sh_off : sh_on;
+                uint16_t *ix = s_idx + h * P2;
+                pull_index_group(ix, (uint32_t)kk, v.x, v.y, T, sh);
+                pull_index_group(ix, (uint32_t)kk + 1u, v.y, v.z, T, sh);
+                pull_index_group(ix, (uint32_t)kk + 2u, v.z, v.w, T, sh);
+                pull_index_group(ix, (uint32_t)kk + 3u, v.w, nx, T, sh);
             }
         }
         __syncthreads();
@@ -1595,52 +1651,71 @@ __global__ __launch_bounds__(BLOCK) void k_cpull(KArgs a, CEmitArgs ea)
             pm.rmask = (1u << pm.sh) - 1u;
         }
         const float t = tg(i < M ? i : n - 1);
-        for (uint32_t row = r_lo + (uint32_t)tid; row < r_hi; row += BLOCK) {
-            const uint32_t jj = row - base;
-            const uint32_t ci = sh_i ? v2e_perm_invert(&pm, jj) : jj;
-            const bool eneg = ci >= T_on;
-            const uint32_t cp = eneg ? ci - T_on : ci;
-            const uint32_t *tab = s_pre + (eneg ? P2 : 0);
-            uint32_t g = 0, gbase = 0; // the last group whose prefix is <= cp (an empty group shares its prefix with the next one)
-            if (!TWO) {
-                for (int st = P2 >> 1; st >= 1; st >>= 1) {
-                    const uint32_t v = tab[g + st];
-                    if (v <= cp) { g += st; gbase = v; }
+        // PULL_ROWS rows per thread and trip, BLOCK apart (each store still writes 64 consecutive rows per wave): their inverse
+        // permutations and lookups are independent, and their mask loads are in flight together
+        for (uint32_t row0 = r_lo + (uint32_t)tid; row0 < r_hi; row0 += PULL_ROWS * BLOCK) {
+            uint32_t gv[PULL_ROWS], rv[PULL_ROWS];
+            bool nv[PULL_ROWS];
+            uint4 ma[PULL_ROWS], mb[PULL_ROWS];
+#pragma unroll
+            for (int u = 0; u < PULL_ROWS; ++u) {
+                const uint32_t row = row0 + (uint32_t)(u * BLOCK);
+                if (row >= r_hi) continue;
+                const uint32_t jj = row - base;
+                const uint32_t ci = sh_i ? v2e_perm_invert(&pm, jj) : jj;
+                const bool eneg = ci >= T_on;
+                const uint32_t cp = eneg ? ci - T_on : ci;
+                const uint32_t *tab = s_pre + (eneg ? P2 : 0);
+                uint32_t g = 0, gbase = 0; // the last group whose prefix is <= cp (an empty group shares its prefix with the next one)
+                if (!TWO) {
+                    g = pull_index_find(tab, s_idx + (eneg ? P2 : 0), eneg ? sh_off : sh_on, cp, &gbase);
+                } else {
+                    for (int st = P2 >> 1; st >= 1; st >>= 1) {
+                        const uint32_t v = tab[g + st];
+                        if (v <= cp) g += st;
+                    }
+                    // the line of 16 entries whose first one is <= cp: four halving steps in registers
+                    const uint4 *lp = (const uint4 *)(pre + (size_t)(key0 + (eneg ? 1 : 0)) * ea.nwp + g * 16u);
+                    const uint4 q0 = lp[0], q1 = lp[1], q2 = lp[2], q3 = lp[3];
+                    const bool h8 = q2.x <= cp;
+                    const uint4 a0 = h8 ? q2 : q0, a1 = h8 ? q3 : q1;
+                    const bool h4 = a1.x <= cp;
+                    const uint4 b = h4 ? a1 : a0;
+                    const bool h2 = b.z <= cp;
+                    const uint32_t c0 = h2 ? b.z : b.x, c1 = h2 ? b.w : b.y;
+                    const bool h1 = c1 <= cp;
+                    gbase = h1 ? c1 : c0;
+                    g = g * 16u + (h8 ? 8u : 0u) + (h4 ? 4u : 0u) + (h2 ? 2u : 0u) + (h1 ? 1u : 0u);
                 }
-            } else {
-                for (int st = P2 >> 1; st >= 1; st >>= 1) {
-                    const uint32_t v = tab[g + st];
-                    if (v <= cp) g += st;
+                const uint4 *mp = (const uint4 *)(cmask + ((size_t)(key0 + (eneg ? 1 : 0)) * ea.nwp + g) * (2 * GPX));
+                ma[u] = mp[0];
+                mb[u] = mp[1];
+                gv[u] = g;
+                rv[u] = cp - gbase;
+                nv[u] = eneg;
+            }
+#pragma unroll
+            for (int u = 0; u < PULL_ROWS; ++u) {
+                const uint32_t row = row0 + (uint32_t)(u * BLOCK);
+                if (row >= r_hi) continue;
+                const uint32_t bit = v2e_nth_set_bit_256((unsigned long long)ma[u].x | ((unsigned long long)ma[u].y << 32), (unsigned long long)ma[u].z | ((unsigned long long)ma[u].w << 32),
+                                                         (unsigned long long)mb[u].x | ((unsigned long long)mb[u].y << 32), (unsigned long long)mb[u].z | ((unsigned long long)mb[u].w << 32),
+                                                         rv[u]);
+                const uint32_t p = gv[u] * (uint32_t)GROUP_PX + bit;
+                uint32_t qy, qx; // y = p / W, x = p % W, exactly
+                if (a.npx < (1 << 24)) { // float32 holds p exactly: the quotient estimate is the true one or one off (one multiply)
+                    qy = (uint32_t)((float)p * rcpW);
+                    int r = (int)(p - qy * (uint32_t)a.W);
+                    if (r < 0) { --qy; r += a.W; }
+                    else if (r >= a.W) { ++qy; r -= a.W; }
+                    qx = (uint32_t)r;
+                } else {
+                    qy = p / (uint32_t)a.W;
+                    qx = p - qy * (uint32_t)a.W;
                 }
-                // the line of 16 entries whose first one is <= cp: four halving steps in registers
-                const uint4 *lp = (const uint4 *)(pre + (size_t)(key0 + (eneg ? 1 : 0)) * ea.nwp + g * 16u);
-                const uint4 q0 = lp[0], q1 = lp[1], q2 = lp[2], q3 = lp[3];
-                const bool h8 = q2.x <= cp;
-                const uint4 a0 = h8 ? q2 : q0, a1 = h8 ? q3 : q1;
-                const bool h4 = a1.x <= cp;
-                const uint4 b = h4 ? a1 : a0;
-                const bool h2 = b.z <= cp;
-                const uint32_t c0 = h2 ? b.z : b.x, c1 = h2 ? b.w : b.y;
-                const bool h1 = c1 <= cp;
-                gbase = h1 ? c1 : c0;
-                g = g * 16u + (h8 ? 8u : 0u) + (h4 ? 4u : 0u) + (h2 ? 2u : 0u) + (h1 ? 1u : 0u);
+                const v2e_f4 v = {t, (float)qx, (float)qy, nv[u] ? -1.0f : 1.0f};
+                __builtin_amdgcn_raw_buffer_store_b128(v, ev_rsrc, (int)(row * 16u), 0, 19); // sc0 nt sc1: written through, non-temporal (see store_event_wt)
             }
-            const uint4 *mp = (const uint4 *)(cmask + ((size_t)(key0 + (eneg ? 1 : 0)) * ea.nwp + g) * (2 * GPX));
-            const uint4 ma = mp[0], mb = mp[1];
-            const uint32_t bit = v2e_nth_set_bit_256((unsigned long long)ma.x | ((unsigned long long)ma.y << 32), (unsigned long long)ma.z | ((unsigned long long)ma.w << 32),
-                                                     (unsigned long long)mb.x | ((unsigned long long)mb.y << 32), (unsigned long long)mb.z | ((unsigned long long)mb.w << 32),
-                                                     cp - gbase);
-            const uint32_t p = g * (uint32_t)GROUP_PX + bit;
-            uint32_t qy; // y = p / W, x = p % W, exactly
-            if (a.npx < (1 << 24)) { // float32 holds p exactly: the quotient estimate is the true one or one off
-                qy = (uint32_t)((float)p * rcpW);
-                if (qy * (uint32_t)a.W > p) --qy;
-                else if ((qy + 1u) * (uint32_t)a.W <= p) ++qy;
-            } else {
-                qy = p / (uint32_t)a.W;
-            }
-            const v2e_f4 v = {t, (float)(p - qy * (uint32_t)a.W), (float)qy, eneg ? -1.0f : 1.0f};
-            __builtin_amdgcn_raw_buffer_store_b128(v, ev_rsrc, (int)(row * 16u), 0, 19); // sc0 nt sc1: written through, non-temporal (see store_event_wt)
         }
     }
 }
