@@ -434,6 +434,30 @@ int v2e_bgr2gray_u8(const uint8_t *src_bgr, uint8_t *dst, int64_t npx, int gray_
 int v2e_events_pack_aedat2(const float *events, void *out_bytes, int64_t n, int sizex, int sizey, int xshift,
                            int yshift, int pshift, int flipx, int flipy, int64_t noise_from, void *stream);
 
+/* The same records for a whole run: frame f's rows start at recs[f].ev_offset (non-decreasing; a row belongs to the last
+ * frame whose ev_offset is <= its index) and its first recs[f].n_signal rows are signal, the rest get the special-event bit.
+ * recs: device array of nrec records (only ev_offset and n_signal are read); NULL: no labels. */
+int v2e_events_pack_aedat2_run(const float *events, void *out_bytes, int64_t n, int sizex, int sizey, int xshift,
+                               int yshift, int pshift, int flipx, int flipy, const v2e_frame_rec *recs, int nrec,
+                               void *stream);
+
+/* Text lines of ae_text_output.py:86-101, one per row in row order:
+ *     t = (events[:, 0]).astype(np.float)              '{}'.format(t[i]): the shortest repr of the float64
+ *     x = events[:, 1].astype(np.int32), y likewise    (no flips)
+ *     p = ((events[:, 3] + 1) / 2).astype(np.int32)
+ *     '{} {} {} {}\n'.format(t[i], x[i], y[i], p[i]), or with labels ' {}' int(signnoise_label[i]) before the '\n'
+ * labels != 0: label 1 for a frame's first n_signal rows, 0 after them; the frames as for v2e_events_pack_aedat2_run (recs
+ * on the device), or recs == NULL: one frame of n_signal signal rows.  scratch: device int64
+ * [v2e_events_format_text_scratch_words(n)]; after the call scratch[0] is the text's length in bytes.  If that exceeds cap,
+ * nothing is written to out (the caller grows the buffer and calls again).  n == 0: scratch[0] = 0, no launch. */
+int v2e_events_format_text(const float *events, int64_t n, const v2e_frame_rec *recs, int nrec, int64_t n_signal,
+                           int labels, char *out, int64_t cap, int64_t *scratch, void *stream);
+int64_t v2e_events_format_text_scratch_words(int64_t n);
+/* The same lines on the host, from the same __host__ __device__ code (v2e_amd/csrc/text_format.h): host rows and recs.
+ * *total = the text's length; V2E_EOVERFLOW (nothing written) if it exceeds cap. */
+int v2e_events_format_text_host(const float *events, int64_t n, const v2e_frame_rec *recs, int nrec, int64_t n_signal,
+                                int labels, char *out, int64_t cap, int64_t *total);
+
 /* HDF5 "events" rows of emulator.py:955-965: uint32 [n][4] = (t*1e6 in float32, x, y, p with -1 -> 0) */
 int v2e_events_pack_h5(const float *events, uint32_t *out, int64_t n, void *stream);
 

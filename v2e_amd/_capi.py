@@ -134,6 +134,10 @@ SIGNATURES = {
     "v2e_u8_to_f32_norm": (_i, [_vp, _vp, _i64, C.c_float, _vp]),
     "v2e_f32_to_u8_trunc": (_i, [_vp, _vp, _i, _i, _i, C.c_float, _i, _vp]),
     "v2e_events_pack_aedat2": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i64, _vp]),
+    "v2e_events_pack_aedat2_run": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "v2e_events_format_text": (_i, [_vp, _i64, _vp, _i, _i64, _i, _vp, _i64, _vp, _vp]),
+    "v2e_events_format_text_scratch_words": (_i64, [_i64]),
+    "v2e_events_format_text_host": (_i, [_vp, _i64, _vp, _i, _i64, _i, _vp, _i64, C.POINTER(_i64)]),
     "v2e_events_pack_h5": (_i, [_vp, _vp, _i64, _vp]),
     "v2e_events_pack64": (_i, [_vp, _vp, _i64, _vp]),
     "v2e_events_unpack64": (_i, [_vp, _vp, _i64, _vp]),

@@ -3,15 +3,32 @@
 // kernels apply the reference's conversion rules so a writer can stream bytes straight from HBM:
 //   AEDAT-2.0  v2ecore/output/aedat2_output.py:155-173  (jAER: big-endian int32 address, int32 timestamp)
 //   HDF5       v2ecore/emulator.py:955-965              (uint32 [N,4]: t_us, x, y, p with -1 -> 0)
+//   text       v2ecore/output/ae_text_output.py:86-101  (`t x y p[ label]\n`, t the repr of the float64; text_format.h)
+// Labels (label_signal_noise) follow the emulator's order of a frame's rows -- its n_signal signal events first, then the
+// noise -- per frame of a run: a row belongs to the last frame whose ev_offset is <= its index.
 #include "common.h"
+#include "text_format.h"
 
 namespace {
+
+// 1: row i is a signal event, 0: noise.  recs == nullptr: one frame of n_signal0 signal rows at row 0 (the per-frame path)
+__host__ __device__ __forceinline__ int row_is_signal(int64_t i, const v2e_frame_rec *recs, int nrec, int64_t n_signal0)
+{
+    if (!recs) return i < n_signal0;
+    int lo = 0, hi = nrec;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)recs[mid].ev_offset <= i) lo = mid; else hi = mid;
+    }
+    return i - (int64_t)recs[lo].ev_offset < (int64_t)recs[lo].n_signal;
+}
 
 __device__ __forceinline__ uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
 
 __global__ __launch_bounds__(256) void k_pack_aedat2(const float4 *__restrict__ ev, uint2 *__restrict__ out, long long n, int sizex,
                                                      int sizey, int xshift, int yshift, int pshift, int flipx, int flipy,
-                                                     long long noise_from, uint32_t noise_bit)
+                                                     int label, const v2e_frame_rec *__restrict__ recs, int nrec,
+                                                     long long n_signal0, uint32_t noise_bit)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -22,7 +39,7 @@ __global__ __launch_bounds__(256) void k_pack_aedat2(const float4 *__restrict__ 
     if (flipy) y = (sizey - 1) - y;
     const int p = (int)((e.w + 1.0f) / 2.0f);    // ((p + 1) / 2).astype(np.int32)
     uint32_t a = ((uint32_t)x << xshift) | ((uint32_t)y << yshift) | ((uint32_t)p << pshift);
-    if (noise_from >= 0 && i >= noise_from) a |= noise_bit;
+    if (label && !row_is_signal(i, recs, nrec, n_signal0)) a |= noise_bit;
     out[i] = make_uint2(bswap32(a), bswap32((uint32_t)t)); // out.byteswap(): big-endian for jAER
 }
 
@@ -191,17 +208,159 @@ __global__ __launch_bounds__(256) void k_unpack32(const uint32_t *__restrict__ p
                         (w >> 21) & 1u ? 1.0f : -1.0f);
 }
 
+// ---- text lines (text_format.h).  Three passes over blocks of TXT_BLOCK rows: the line lengths summed per block, an exclusive
+// scan of the block sums (their total is the text's length), and the lines themselves, staged per block in LDS at their offsets
+// and copied out with consecutive bytes per lane.
+constexpr int TXT_BLOCK = 256;
+
+__device__ __forceinline__ int text_label(int64_t i, int labels, const v2e_frame_rec *recs, int nrec, int64_t n_signal0)
+{
+    return labels ? row_is_signal(i, recs, nrec, n_signal0) : -1;
+}
+
+__global__ __launch_bounds__(TXT_BLOCK) void k_text_len(const float4 *__restrict__ ev, int64_t n, int labels,
+                                                        const v2e_frame_rec *__restrict__ recs, int nrec, int64_t n_signal0,
+                                                        long long *__restrict__ blk)
+{
+    __shared__ int s_sum[TXT_BLOCK / 64];
+    const int64_t i = (int64_t)blockIdx.x * TXT_BLOCK + threadIdx.x;
+    int len = 0;
+    if (i < n) {
+        const float4 e = ev[i];
+        len = v2e_tf::put_line<false>(nullptr, e.x, e.y, e.z, e.w, text_label(i, labels, recs, nrec, n_signal0));
+    }
+    for (int o = 32; o > 0; o >>= 1) len += __shfl_down(len, o, 64);
+    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = len;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long t = 0;
+        for (int w = 0; w < TXT_BLOCK / 64; ++w) t += s_sum[w];
+        blk[blockIdx.x] = t;
+    }
+}
+
+// exclusive scan of the per-block byte counts in place (one workgroup), the total to *total
+__global__ __launch_bounds__(1024) void k_text_scan(long long *__restrict__ blk, int nblk, long long *__restrict__ total)
+{
+    __shared__ long long s_part[1024];
+    const int tid = threadIdx.x;
+    const int per = (nblk + 1023) / 1024;
+    long long sum = 0;
+    for (int k = 0; k < per; ++k) { const int j = tid * per + k; if (j < nblk) sum += blk[j]; }
+    s_part[tid] = sum;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const long long v = tid >= off ? s_part[tid - off] : 0;
+        __syncthreads();
+        s_part[tid] += v;
+        __syncthreads();
+    }
+    long long run = s_part[tid] - sum;
+    for (int k = 0; k < per; ++k) {
+        const int j = tid * per + k;
+        if (j < nblk) { const long long c = blk[j]; blk[j] = run; run += c; }
+    }
+    if (tid == 1023) *total = s_part[1023];
+}
+
+__global__ __launch_bounds__(TXT_BLOCK) void k_text_write(const float4 *__restrict__ ev, int64_t n, int labels,
+                                                          const v2e_frame_rec *__restrict__ recs, int nrec, int64_t n_signal0,
+                                                          const long long *__restrict__ blk_base, const long long *__restrict__ total,
+                                                          char *__restrict__ out, int64_t cap)
+{
+    __shared__ char s_text[TXT_BLOCK * V2E_TEXT_MAX_LINE];
+    __shared__ int s_off[TXT_BLOCK];
+    if (*total > cap) return; // the caller's buffer is too small: nothing is written, scratch[0] says how much is needed
+    const int tid = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * TXT_BLOCK + tid;
+    float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
+    int lab = -1, len = 0;
+    if (i < n) {
+        e = ev[i];
+        lab = text_label(i, labels, recs, nrec, n_signal0);
+        len = v2e_tf::put_line<false>(nullptr, e.x, e.y, e.z, e.w, lab);
+    }
+    s_off[tid] = len;
+    __syncthreads();
+    for (int off = 1; off < TXT_BLOCK; off <<= 1) { // inclusive scan of the line lengths
+        const int v = tid >= off ? s_off[tid - off] : 0;
+        __syncthreads();
+        s_off[tid] += v;
+        __syncthreads();
+    }
+    if (i < n) v2e_tf::put_line<true>(s_text + (s_off[tid] - len), e.x, e.y, e.z, e.w, lab);
+    __syncthreads();
+    const int nbytes = s_off[TXT_BLOCK - 1];
+    char *dst = out + blk_base[blockIdx.x];
+    for (int b = tid; b < nbytes; b += TXT_BLOCK) dst[b] = s_text[b];
+}
+
 } // namespace
 
 extern "C" {
+
+int v2e_events_format_text(const float *events, int64_t n, const v2e_frame_rec *recs, int nrec, int64_t n_signal, int labels,
+                           char *out, int64_t cap, int64_t *scratch, void *stream)
+{
+    V2E_REQUIRE(scratch && cap >= 0 && (n == 0 || (events && out)), "null");
+    V2E_REQUIRE(n >= 0 && (n + TXT_BLOCK - 1) / TXT_BLOCK <= ((int64_t)1 << 30), "too many rows");
+    V2E_REQUIRE(!recs || nrec > 0, "recs without frames");
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) { V2E_HIP(hipMemsetAsync(scratch, 0, sizeof(int64_t), s)); return 0; }
+    const int nblk = (int)((n + TXT_BLOCK - 1) / TXT_BLOCK);
+    long long *blk = (long long *)scratch + 1;
+    k_text_len<<<nblk, TXT_BLOCK, 0, s>>>((const float4 *)events, n, labels, recs, nrec, n_signal, blk);
+    k_text_scan<<<1, 1024, 0, s>>>(blk, nblk, (long long *)scratch);
+    k_text_write<<<nblk, TXT_BLOCK, 0, s>>>((const float4 *)events, n, labels, recs, nrec, n_signal, blk, (const long long *)scratch,
+                                            out, cap);
+    V2E_HIP(hipGetLastError());
+    return 0;
+}
+
+int64_t v2e_events_format_text_scratch_words(int64_t n) { return 1 + (n + TXT_BLOCK - 1) / TXT_BLOCK; }
+
+int v2e_events_format_text_host(const float *events, int64_t n, const v2e_frame_rec *recs, int nrec, int64_t n_signal, int labels,
+                                char *out, int64_t cap, int64_t *total)
+{
+    V2E_REQUIRE(total && cap >= 0 && n >= 0 && (n == 0 || events) && (!recs || nrec > 0), "bad args");
+    int64_t len = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const float *e = events + 4 * i;
+        len += v2e_tf::put_line<false>(nullptr, e[0], e[1], e[2], e[3], labels ? row_is_signal(i, recs, nrec, n_signal) : -1);
+    }
+    *total = len;
+    if (len > cap) return V2E_EOVERFLOW;
+    V2E_REQUIRE(out || len == 0, "null");
+    char *o = out;
+    for (int64_t i = 0; i < n; ++i) {
+        const float *e = events + 4 * i;
+        o += v2e_tf::put_line<true>(o, e[0], e[1], e[2], e[3], labels ? row_is_signal(i, recs, nrec, n_signal) : -1);
+    }
+    return 0;
+}
+
+int v2e_events_pack_aedat2_run(const float *events, void *out_bytes, int64_t n, int sizex, int sizey, int xshift, int yshift,
+                               int pshift, int flipx, int flipy, const v2e_frame_rec *recs, int nrec, void *stream)
+{
+    V2E_REQUIRE((events && out_bytes) || n == 0, "null");
+    V2E_REQUIRE(!recs || nrec > 0, "recs without frames");
+    if (n <= 0) return 0;
+    k_pack_aedat2<<<v2e_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>((const float4 *)events, (uint2 *)out_bytes, n, sizex, sizey,
+                                                                    xshift, yshift, pshift, flipx, flipy, recs ? 1 : 0, recs, nrec,
+                                                                    0, 1u << 10);
+    V2E_HIP(hipGetLastError());
+    return 0;
+}
 
 int v2e_events_pack_aedat2(const float *events, void *out_bytes, int64_t n, int sizex, int sizey, int xshift, int yshift,
                            int pshift, int flipx, int flipy, int64_t noise_from, void *stream)
 {
     V2E_REQUIRE((events && out_bytes) || n == 0, "null");
     if (n <= 0) return 0;
+    // a run of one frame whose first noise_from rows are signal (noise_from < 0: no labels)
     k_pack_aedat2<<<v2e_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>((const float4 *)events, (uint2 *)out_bytes, n, sizex, sizey,
-                                                                    xshift, yshift, pshift, flipx, flipy, noise_from, 1u << 10);
+                                                                    xshift, yshift, pshift, flipx, flipy, noise_from >= 0 ? 1 : 0,
+                                                                    nullptr, 0, noise_from, 1u << 10);
     V2E_HIP(hipGetLastError());
     return 0;
 }

@@ -147,6 +147,8 @@ class _PendingRun:
         self.counts, self.start, self.return_device, self.empty, self.dts = counts, start, return_device, empty, dts
         self.ticket = ticket  # pipelined runs (v2e_emu_run, RUN_PIPELINED): what result() waits for on the host (v2e_emu_run_wait)
         self._res = None
+        self.which = None     # the buffer set the run's rows and records are in
+        self.frame0 = 0       # 0-based index of the run's first frame in the clip (the HDF5 frame_idx slot)
 
     @property
     def done(self):
@@ -397,6 +399,7 @@ class EventEmulator(object):
         if getattr(self, "record_single_pixel_states", None) is not None:  # emulator.py:428-429
             self.save_recorded_single_pixel_states()
             self.record_single_pixel_states = None
+        self._write_held_runs()  # every run enqueued while the sinks were open reaches them before they close
         for w in ("dvs_h5", "dvs_aedat2", "dvs_aedat4", "dvs_text"):
             o = getattr(self, w, None)
             if o is not None:
@@ -431,6 +434,7 @@ class EventEmulator(object):
             logger.warning("dvs_params {} not known: Using commandline assigned options".format(model))
 
     def reset(self):  # emulator.py:558-578
+        self._write_held_runs()  # runs still held for the open sinks are written first (dropped if a run failed)
         self._failed = None
         self._async_slots = {}  # handles of runs enqueued before the reset are no longer collected on the caller's behalf
         self.num_events_total = 0
@@ -872,6 +876,59 @@ class EventEmulator(object):
         if self.dvs_text is not None:
             self.dvs_text.appendEvents(ev_dev, n_signal=sig)
 
+    def _sinks_open(self):
+        return self.dvs_h5 is not None or self.dvs_aedat2 is not None or self.dvs_aedat4 is not None or self.dvs_text is not None
+
+    def _write_held_runs(self):
+        """Finish and write, in order, every device-resident run still held for the open sinks (cleanup(), reset()).  Runs of
+        a failed instance cannot be written: they are dropped with an error in the log."""
+        q = self.__dict__.get("_sink_runs")
+        while q:
+            pend = q[0]
+            try:
+                pend.result()  # writes it and takes it off the queue
+            except Exception as e:
+                logger.error("v2e_amd.EventEmulator: %d enqueued run(s) not written to the event files: %s", len(q), e)
+                q.clear()
+            if q and q[0] is pend:  # (a result computed before it could be written)
+                q.pop(0)
+
+    def _write_run(self, pend, r, rows_dev, rows_host):
+        """_write_events for a whole device-resident run (emulator.py:953-977 per frame): the run's rows go to every open
+        sink, with the per-frame signal / noise labels of its records.  The rows are final on the device (result() waited for
+        them); the packing, formatting and copies run on the sinks' own streams."""
+        total = int(rows_dev.shape[0])
+        off = r["ev_offset"].astype(np.int64)
+        nsig = r["n_signal"].astype(np.int64)
+        nev = r["n_events"].astype(np.int64)
+        if self.dvs_h5 is not None:
+            if total > 0:
+                from .sinks import pack_h5
+                side = self.__dict__.get("_h5_stream") or torch.cuda.Stream(rows_dev.device)
+                self._h5_stream = side
+                with torch.cuda.stream(side):
+                    temp = pack_h5(rows_dev).cpu().numpy().view(np.uint32)
+                self.dvs_h5_dataset.resize(self.dvs_h5_dataset.shape[0] + temp.shape[0], axis=0)
+                self.dvs_h5_dataset[-temp.shape[0]:] = temp
+            if self.frame_ev_idx_dataset is not None:  # after each frame's events (emulator.py:979-983)
+                ends = self.dvs_h5_dataset.shape[0] - total + np.cumsum(nev)
+                self.frame_ev_idx_dataset[pend.frame0:pend.frame0 + len(ends)] = ends.astype(np.uint64)
+        if total == 0:
+            return
+        if self.dvs_aedat2 is not None:
+            self.dvs_aedat2.appendRun(rows_dev, off, nsig)
+        if self.dvs_aedat4 is not None:
+            if rows_host is None:
+                rows_host = rows_dev.cpu().numpy()
+            label = None
+            if self.label_signal_noise:
+                label = np.zeros(total, dtype=bool)
+                for o, k in zip(off, nsig):
+                    label[o:o + k] = True
+            self.dvs_aedat4.appendEvents(rows_host, signnoise_label=label)
+        if self.dvs_text is not None:
+            self.dvs_text.appendRun(rows_dev, off, nsig)
+
     # ------------------------------------------------------------- centre-surround
     MAX_CHANGE_TO_TERMINATE_EULER_SURROUND_STEPPING = 1e-5  # emulator.py:52
     CSDVS_RUN_MAX_STEPS = 8192  # Euler steps per frame a device-resident run enqueues up front
@@ -974,6 +1031,9 @@ class EventEmulator(object):
         frames_dev = eng.to_device_frame(frames)
         counts = np.zeros(F, dtype=np.int64)
         start = 0
+        if self.frame_h5_dataset is not None:  # emulator.py:636-638 per frame: the input frames of the HDF5 file
+            fr = frames.detach().cpu().numpy() if torch.is_tensor(frames) else np.asarray(frames)
+            self.frame_h5_dataset[self.frame_counter:self.frame_counter + F] = fr.astype(np.uint8)
         if not self._initialized:
             if t_frames[0] < self.t_previous:
                 raise ValueError("frame time must not decrease")
@@ -1055,6 +1115,11 @@ class EventEmulator(object):
             ev_old, counts_old = old.result()
             if old.return_device and ev_old is not None:
                 old._res = (ev_old.clone(), counts_old)
+        held = self.__dict__.get("_sink_runs")
+        if held:  # a run held for the sinks (its handle dropped) in this buffer set: written, with every run before it, now
+            last = [p for p in held if p.which == which]
+            if last:
+                last[-1].result()
         ev = eng.event_buffer(cap, which)
         recs = eng.alloc_recs(nrun, which)
         ug = int(use_graph)
@@ -1077,11 +1142,20 @@ class EventEmulator(object):
         dts = np.asarray(t_frames[start:]) - np.asarray(t_prev)
         pend = _PendingRun(self, ev, recs, done, counts, start, return_device, None, dts, ticket)
         pend.cs_steps_dev = cs_steps_dev
+        pend.which, pend.frame0 = which, self.frame_counter - nrun
         slots[which] = weakref.ref(pend)
+        if self._sinks_open():
+            # held strongly until its rows are in the files, in the order the runs were enqueued (a handle the caller drops is
+            # written by the call that reuses its buffer set, or by cleanup())
+            self.__dict__.setdefault("_sink_runs", []).append(pend)
         return pend
 
     def _finish_run(self, pend):
         eng = self._engine
+        held = self.__dict__.get("_sink_runs")
+        if held and any(p is pend for p in held):
+            while held[0] is not pend:  # the files get the runs in the order they were enqueued
+                held[0].result()
         if getattr(self, "_failed", None):  # an earlier pending run failed: the state this run started from is not the clip's
             raise _capi.V2EAmdError("a previous device-resident run failed (%s); this run started from its state: call reset()"
                                     % self._failed)
@@ -1116,6 +1190,10 @@ class EventEmulator(object):
         self.num_events_on += int(r["n_on"].sum())
         self.num_events_off += int(r["n_off"].sum())
         out = pend.ev[0, :total]
+        host = None if pend.return_device or total == 0 else out.cpu().numpy()
+        if held and held[0] is pend:
+            held.pop(0)
+            self._write_run(pend, r, out, host)
         if pend.return_device:
             return out, pend.counts
-        return (out.cpu().numpy() if total > 0 else None), pend.counts
+        return host, pend.counts

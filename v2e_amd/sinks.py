@@ -2,6 +2,7 @@
 import logging
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _capi
@@ -15,6 +16,107 @@ logger = logging.getLogger(__name__)
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr())
+
+
+_REC_DT = np.dtype([("max_events", "<i4"), ("flags", "<u4"), ("n_signal", "<u4"), ("n_events", "<u4"), ("n_on", "<u4"),
+                    ("n_off", "<u4"), ("ev_offset", "<u8")])  # struct v2e_frame_rec
+
+
+def frames_from_labels(signnoise_label):
+    """The reference's boolean label array (True = signal) as a frame table (ev_offset, n_signal): one frame per stretch of
+    equal labels, all signal or all noise, so that any labelling goes through the frame-table kernels."""
+    lab = np.asarray(signnoise_label.detach().cpu().numpy() if torch.is_tensor(signnoise_label) else signnoise_label).astype(bool)
+    n = len(lab)
+    if n == 0:
+        return np.zeros(1, np.int64), np.zeros(1, np.int64)
+    starts = np.concatenate([[0], np.flatnonzero(lab[1:] != lab[:-1]) + 1]).astype(np.int64)
+    lens = np.diff(np.concatenate([starts, [n]]))
+    return starts, np.where(lab[starts], lens, 0).astype(np.int64)
+
+
+class _Staging:
+    """Buffers of one sink: a device frame table, device bytes and scratch, pinned host bytes, all grown on demand and reused;
+    and the sink's own stream, on which a run's bytes are made and copied (never the caller's stream, which carries the chain)."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.stream = torch.cuda.Stream(self.device)
+        self.buf = {}
+
+    def get(self, name, n, dtype, pinned=False):
+        t = self.buf.get(name)
+        if t is None or t.numel() < n:
+            n = max(int(n * 1.25), 1 << 12)
+            t = torch.empty(n, dtype=dtype, pin_memory=True) if pinned else torch.empty(n, dtype=dtype, device=self.device)
+            self.buf[name] = t
+        return t
+
+    def frame_table(self, ev_offset, n_signal):
+        """Device struct v2e_frame_rec[F] with ev_offset and n_signal set (what the kernels read), uploaded on the current stream."""
+        rec = _frame_recs(ev_offset, n_signal)
+        F = len(rec)
+        nb = F * _REC_DT.itemsize
+        host = self.get("rec_host", nb, torch.uint8, pinned=True)
+        host[:nb].copy_(torch.from_numpy(rec.view(np.uint8)))
+        dev = self.get("rec_dev", nb, torch.uint8)
+        dev[:nb].copy_(host[:nb], non_blocking=True)
+        return dev, F
+
+    def to_host(self, src, nbytes):
+        """src[:nbytes] (device uint8) into the pinned buffer on the current stream; the caller synchronises."""
+        host = self.get("host_bytes", nbytes, torch.uint8, pinned=True)
+        host[:nbytes].copy_(src[:nbytes], non_blocking=True)
+        return host
+
+
+def _device_rows(events):
+    ev = events if torch.is_tensor(events) else torch.from_numpy(np.ascontiguousarray(events, dtype=np.float32))
+    if not ev.is_cuda:
+        ev = ev.cuda()
+    return ev.contiguous()
+
+
+def _frame_recs(ev_offset, n_signal):
+    rec = np.zeros(len(ev_offset), dtype=_REC_DT)
+    rec["ev_offset"] = np.asarray(ev_offset, dtype=np.int64)
+    rec["n_signal"] = np.asarray(n_signal, dtype=np.int64)
+    return rec
+
+
+def _format_text_call(ev, n, labels, recs, nrec, nsig0, out, scratch, stream):
+    check(_capi.lib().v2e_events_format_text(_ptr(ev) if n else None, n, recs, nrec, nsig0, 1 if labels else 0, _ptr(out),
+                                             int(out.numel()), _ptr(scratch), C.c_void_p(stream.cuda_stream)),
+          "v2e_events_format_text")
+
+
+def format_text(events_dev, labels=False, n_signal=None, frames=None, out=None):
+    """events_dev: device float32 [N,4] -> (device uint8 text, its length in bytes): the lines DVSTextOutput.appendEvents
+    writes for these rows (ae_text_output.py:86-101), formatted on the GPU (v2e_events_format_text) on the current stream.
+    labels: add the signal/noise column -- 1 for the first n_signal rows (one frame), or per frame with frames = (ev_offset,
+    n_signal) arrays of a run.  out: a device uint8 buffer to write into; one that is too small raises V2EAmdError and is
+    left untouched.  Zero rows give zero bytes."""
+    ev = events_dev.contiguous()
+    n = int(ev.shape[0])
+    dev = ev.device
+    stream = torch.cuda.current_stream(dev)
+    scratch = torch.empty(int(_capi.lib().v2e_events_format_text_scratch_words(n)), dtype=torch.int64, device=dev)
+    recs, nrec, nsig0 = None, 0, 0
+    if labels and frames is not None:
+        rec = torch.from_numpy(_frame_recs(*frames).view(np.uint8)).to(dev)
+        recs, nrec = _ptr(rec), len(frames[0])
+    elif labels:
+        nsig0 = n if n_signal is None else int(n_signal)
+    own = out is None
+    if own:
+        out = torch.empty(max(32 * n, 1), dtype=torch.uint8, device=dev)
+    _format_text_call(ev, n, labels, recs, nrec, nsig0, out, scratch, stream)
+    total = int(scratch[0].item())
+    if total > out.numel():
+        if not own:
+            raise _capi.V2EAmdError("v2e_events_format_text: the text needs %d bytes, the buffer holds %d" % (total, out.numel()))
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        _format_text_call(ev, n, labels, recs, nrec, nsig0, out, scratch, stream)
+    return out, total
 
 
 def pack_aedat2(events_dev, width, height, noise_from=-1):
@@ -124,18 +226,60 @@ class DeviceAEDat2Output:
         self.numOffEvents += n - on
         self.file.flush()
 
+    def appendRun(self, events_dev, ev_offset, n_signal):
+        """The rows of a whole run, as if appendEvents had been called once per frame: device rows that are final (the caller
+        has waited for them), frame f starting at row ev_offset[f] with its first n_signal[f] rows signal.  Packed on the
+        sink's own stream (v2e_events_pack_aedat2_run: the noise bit per frame), copied once into pinned memory, one write."""
+        if self.file is None or events_dev is None or int(events_dev.shape[0]) == 0:
+            return
+        ev = events_dev.contiguous()
+        n = int(ev.shape[0])
+        st = self._staging = getattr(self, "_staging", None) or _Staging(ev.device)
+        xs, ys, ps, fx, fy = _AEDAT2_LAYOUT[(self.width, self.height)]
+        with torch.cuda.stream(st.stream):
+            recs, nrec = None, 0
+            if self.label_signal_noise:
+                rec_t, nrec = st.frame_table(ev_offset, n_signal)
+                recs = _ptr(rec_t)
+            out = st.get("dev_bytes", 8 * n, torch.uint8)
+            check(_capi.lib().v2e_events_pack_aedat2_run(_ptr(ev), _ptr(out), n, self.width, self.height, xs, ys, ps, fx, fy, recs,
+                                                         nrec, C.c_void_p(st.stream.cuda_stream)), "v2e_events_pack_aedat2_run")
+            on = (ev[:, 3] > 0).sum()
+            host = st.to_host(out, 8 * n)
+            st.stream.synchronize()
+        data = memoryview(host.numpy())[:8 * n]
+        if self.numEventsWritten == 0:
+            # the '#' rule of the per-frame path applies to the first frame that has rows: its leading rows only
+            off = np.append(np.asarray(ev_offset, dtype=np.int64), n)
+            f = int(np.flatnonzero(off[1:] > off[:-1])[0])
+            a, b = int(off[f]), int(off[f + 1])
+            k = a
+            while k < b and data[8 * k] == 0x23:
+                k += 1
+            if k > a:
+                self.file.write(data[:8 * a])
+                data = data[8 * k:]
+        self.file.write(data)
+        self.numEventsWritten += n
+        on = int(on.item())
+        self.numOnEvents += on
+        self.numOffEvents += n - on
+        self.file.flush()
+
 
 class DeviceTextOutput:
     """Text event sink (v2ecore/output/ae_text_output.py:51-101: `t x y p[ label]` per line, p in {0, 1}, t the Python
-    repr of the float64 value of the float32 time stamp).  The integer columns are converted on the GPU (same kernel as
-    the HDF5 rows); producing a shortest round-trip decimal of t is Python's float repr, on the host."""
+    repr of the float64 value of the float32 time stamp).  The lines are made on the GPU (v2e_events_format_text: the
+    shortest round-trip decimal of t included, v2e_amd/csrc/text_format.h), copied once into pinned memory and written
+    with one file.write per call."""
 
     def __init__(self, filepath, label_signal_noise=False):
         import atexit
         self.filepath = filepath
         self.label_signal_noise = label_signal_noise
         self.numEventsWritten = 0
-        self.file = open(filepath, 'w')
+        self.file = open(filepath, 'wb')
+        self._staging = None
         self._writeHeader()
         atexit.register(self.cleanup)
 
@@ -161,29 +305,65 @@ class DeviceTextOutput:
         user = '# User name: {}\n'.format(getpass.getuser())
         for line in ('#!events.txt\n', '# This is a text DVS created by v2e (see https://github.com/SensorsINI/v2e)\n', fmt, date,
                      tms, user):
-            self.file.write(line)
+            self.file.write(line.encode('UTF-8'))
 
     def appendEvents(self, events, signnoise_label=None, n_signal=None):
+        """events: [N,4] float32 rows as a device tensor or a host array; the label column (label_signal_noise) from
+        `n_signal` (the first n_signal rows are signal) or the reference's boolean array.  Formatted on the current stream,
+        behind whatever made the rows."""
         if self.file is None:
             raise Exception('output file closed already')
         if events is None or len(events) == 0:
             return
-        ev = events if torch.is_tensor(events) else torch.from_numpy(events.astype('float32', copy=False))
-        if not ev.is_cuda:
-            ev = ev.cuda()
-        n = int(ev.shape[0])
-        cols = pack_h5(ev).cpu().numpy()             # x, y as int32, p: -1 -> 0, +1 -> 1 (same as ((p + 1) / 2).astype(int32))
-        t = ev[:, 0].double().cpu().numpy()          # events[:, 0].astype(float)
-        lab = None
-        if self.label_signal_noise:
+        ev = _device_rows(events)
+        frames, nsig0 = None, 0
+        labels = self.label_signal_noise and (n_signal is not None or signnoise_label is not None)
+        if labels:
             if n_signal is not None:
-                lab = [1 if i < int(n_signal) else 0 for i in range(n)]
-            elif signnoise_label is not None:
-                lab = [int(v) for v in signnoise_label]
-        if lab is None:
-            self.file.writelines('{} {} {} {}\n'.format(t[i], cols[i, 1], cols[i, 2], cols[i, 3]) for i in range(n))
-        else:
-            self.file.writelines('{} {} {} {} {}\n'.format(t[i], cols[i, 1], cols[i, 2], cols[i, 3], lab[i]) for i in range(n))
+                nsig0 = int(n_signal)
+            else:
+                frames = frames_from_labels(signnoise_label)
+        self._emit(ev, labels, frames, nsig0, torch.cuda.current_stream(ev.device))
+
+    def appendRun(self, events_dev, ev_offset, n_signal):
+        """The rows of a whole run, as if appendEvents had been called once per frame: device rows that are final (the caller
+        has waited for them), frame f starting at row ev_offset[f] with its first n_signal[f] rows signal.  Formatted on the
+        sink's own stream."""
+        if self.file is None:
+            raise Exception('output file closed already')
+        if events_dev is None or int(events_dev.shape[0]) == 0:
+            return
+        st = self._stage(events_dev.device)
+        frames = (ev_offset, n_signal) if self.label_signal_noise else None
+        self._emit(events_dev.contiguous(), self.label_signal_noise, frames, 0, st.stream)
+
+    def _stage(self, device):
+        if self._staging is None:
+            self._staging = _Staging(device)
+        return self._staging
+
+    def _emit(self, ev, labels, frames, nsig0, stream):
+        n = int(ev.shape[0])
+        st = self._stage(ev.device)
+        with torch.cuda.stream(stream):
+            recs, nrec = None, 0
+            if frames is not None:
+                rec_t, nrec = st.frame_table(*frames)
+                recs = _ptr(rec_t)
+            scratch = st.get("scratch", int(_capi.lib().v2e_events_format_text_scratch_words(n)), torch.int64)
+            total_h = st.get("total", 1, torch.int64, pinned=True)
+            out = st.get("dev_bytes", 32 * n, torch.uint8)
+            for _ in range(2):
+                _format_text_call(ev, n, labels, recs, nrec, nsig0, out, scratch, stream)
+                total_h[:1].copy_(scratch[:1], non_blocking=True)
+                stream.synchronize()
+                total = int(total_h[0])
+                if total <= out.numel():
+                    break
+                out = st.get("dev_bytes", total, torch.uint8)  # the lines are longer than the guess: grow, format again
+            host = st.to_host(out, total)
+            stream.synchronize()
+        self.file.write(memoryview(host.numpy())[:total])
         self.numEventsWritten += n
 
 
