@@ -392,6 +392,19 @@ int v2e_slomo_fuse(const float *i0, const float *i1, const float *x12, const flo
  * one float32 sqrt of it (sqrt is monotone: the same number as the reference's max of sqrt planes).  0xffffffff: a NaN flow. */
 int v2e_slomo_max_speed2(const float *flow, int b, int h, int w, uint32_t *out_bits, void *stream);
 
+/* v2e_slomo_max_speed2 per batch of a flow chunk in one launch: flow [b][4][h][w] cut into consecutive batches of `seg` pairs (the
+ * last one may be shorter); out_bits[ceil(b / seg)] (device) gets each batch's value, bit for bit what v2e_slomo_max_speed2 gives
+ * for that batch alone (0xffffffff: a NaN flow in that batch). */
+int v2e_slomo_max_speed2_seg(const float *flow, int b, int seg, int h, int w, uint32_t *out_bits, void *stream);
+
+/* Ragged interpolation batches (auto_upsample: every batch has its own number of time points).  tab: DEVICE int32 [n][3], one row
+ * per sample = {pair index into i0 / i1 / flow, row of tcoef [rows][6], output frame}; v2e_slomo_prep_tab / _fuse_tab do for
+ * sample s exactly what v2e_slomo_prep / _fuse do for the sample of that pair and time row, x12 [n][12][h][w], out [n][1][h][w]. */
+int v2e_slomo_prep_tab(const float *i0, const float *i1, const float *flow, const float *tcoef, const int32_t *tab, int n,
+                       int h, int w, float *x12, void *stream);
+int v2e_slomo_fuse_tab(const float *i0, const float *i1, const float *x12, const float *intrp, const float *tcoef,
+                       const int32_t *tab, int n, int h, int w, float *out, void *stream);
+
 /* ------------------------------------------- SloMo <-> emulator hand-off */
 
 /*
@@ -410,6 +423,9 @@ int v2e_u8_to_f32_norm(const uint8_t *in, float *out, int64_t n, float mean, voi
 /* revNormalize + ToPILImage: out = (uint8)(int)((in + mean) * 255) (slomo.py:437); reorder != 0:
  * in is [U][B][hw] (interpolation batch order), out is [B][U][hw] (time order, slomo.py:441) */
 int v2e_f32_to_u8_trunc(const float *in, uint8_t *out, int U, int B, int hw, float mean, int reorder, void *stream);
+
+/* the same conversion for the samples of a v2e_slomo_fuse_tab call: in [n][hw], sample s written to frame tab[s][2] of out */
+int v2e_f32_to_u8_trunc_tab(const float *in, uint8_t *out, const int32_t *tab, int n, int hw, float mean, void *stream);
 
 /* ------------------------------------------- stage-1 pre-processing (v2e.py:687-738) -- PARITY UNPINNED:
  * OpenCV 4.x's published INTER_AREA / BGR2GRAY 8-bit algorithms restated (see v2e_amd/csrc/preproc.hip); cv2 is in neither

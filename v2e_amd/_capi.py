@@ -150,6 +150,10 @@ SIGNATURES = {
     "v2e_render_packet": (_i, [_vp, _i64, _i, _vp, _i, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _d, _d, _d, _d, _d, _vp]),
     "v2e_slomo_fuse": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "v2e_slomo_max_speed2": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "v2e_slomo_max_speed2_seg": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "v2e_slomo_prep_tab": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "v2e_slomo_fuse_tab": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "v2e_f32_to_u8_trunc_tab": (_i, [_vp, _vp, _vp, _i, _i, C.c_float, _vp]),
 }
 
 _lib = None

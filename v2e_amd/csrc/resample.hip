@@ -80,6 +80,17 @@ __global__ __launch_bounds__(256) void k_f32_to_u8_reorder(const float *__restri
     out[i] = (uint8_t)(int)((in[((size_t)k * B + b) * hw + p] + mean) * 255.0f);
 }
 
+// the samples of a ragged interpolation call (v2e_slomo_fuse_tab) straight into their frame slots: in [n][hw], sample s to frame
+// tab[s][2] of out (tab rows {pair, coefficient row, frame}); the conversion of k_f32_to_u8
+__global__ __launch_bounds__(256) void k_f32_to_u8_tab(const float *__restrict__ in, uint8_t *__restrict__ out,
+                                                       const int *__restrict__ tab, int hw, float mean)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const int s = blockIdx.y;
+    if (p >= hw) return;
+    out[(size_t)tab[3 * s + 2] * hw + p] = (uint8_t)(int)((in[(size_t)s * hw + p] + mean) * 255.0f);
+}
+
 } // namespace
 
 extern "C" {
@@ -125,6 +136,14 @@ int v2e_f32_to_u8_trunc(const float *in, uint8_t *out, int U, int B, int hw, flo
     const long long n = (long long)U * B * hw;
     if (reorder) k_f32_to_u8_reorder<<<v2e_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(in, out, U, B, hw, mean);
     else k_f32_to_u8<<<v2e_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(in, out, n, mean);
+    V2E_HIP(hipGetLastError());
+    return 0;
+}
+
+int v2e_f32_to_u8_trunc_tab(const float *in, uint8_t *out, const int32_t *tab, int n, int hw, float mean, void *stream)
+{
+    V2E_REQUIRE(in && out && tab && n > 0 && n <= 65535 && hw > 0, "bad args");
+    k_f32_to_u8_tab<<<dim3(v2e_cdiv(hw, 256), n), 256, 0, (hipStream_t)stream>>>(in, out, tab, hw, mean);
     V2E_HIP(hipGetLastError());
     return 0;
 }

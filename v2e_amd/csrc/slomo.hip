@@ -576,18 +576,15 @@ __device__ __forceinline__ float warp_sample(const float *__restrict__ img, int 
     return out;
 }
 
-// slomo.py:405-419: x12[(ti*b+bi)] = [I0, I1, F01(2), F10(2), Ft1(2), Ft0(2), g(I1,Ft1), g(I0,Ft0)]
-__global__ __launch_bounds__(256) void k_prep(const float *__restrict__ i0, const float *__restrict__ i1,
-                                              const float *__restrict__ flow, const float *__restrict__ coef, int n_t,
-                                              int b, int h, int w, float *__restrict__ x12)
+// slomo.py:405-419: x12[s] = [I0, I1, F01(2), F10(2), Ft1(2), Ft0(2), g(I1,Ft1), g(I0,Ft0)] of pair bi at time row c
+// (k_prep: sample s = ti*b + bi; k_prep_tab: the pair and the row from a per-sample table)
+__device__ __forceinline__ void prep_sample(const float *__restrict__ i0, const float *__restrict__ i1,
+                                            const float *__restrict__ flow, const float *__restrict__ c, int bi, int s,
+                                            int h, int w, int p, float *__restrict__ x12)
 {
     const int hw = h * w;
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    const int s = blockIdx.y; // ti*b + bi
-    if (p >= hw) return;
-    const int ti = s / b, bi = s - ti * b;
     // fCoeff of slomo.py:406-407, evaluated by the host in Python doubles and rounded to float32
-    const float c00 = coef[ti * 6 + 0], c01 = coef[ti * 6 + 1], c10 = coef[ti * 6 + 2], c11 = coef[ti * 6 + 3];
+    const float c00 = c[0], c01 = c[1], c10 = c[2], c11 = c[3];
     const float *fl = flow + (size_t)bi * 4 * hw;
     const float f01x = fl[p], f01y = fl[hw + p], f10x = fl[2 * hw + p], f10y = fl[3 * hw + p];
     const float ft0x = c00 * f01x + c01 * f10x, ft0y = c00 * f01y + c01 * f10y;
@@ -607,17 +604,35 @@ __global__ __launch_bounds__(256) void k_prep(const float *__restrict__ i0, cons
     o[11 * hw] = g0;
 }
 
-// slomo.py:421-433
-__global__ __launch_bounds__(256) void k_fuse(const float *__restrict__ i0, const float *__restrict__ i1,
-                                              const float *__restrict__ x12, const float *__restrict__ intrp,
-                                              const float *__restrict__ coef, int n_t, int b, int h, int w,
-                                              float *__restrict__ out)
+__global__ __launch_bounds__(256) void k_prep(const float *__restrict__ i0, const float *__restrict__ i1,
+                                              const float *__restrict__ flow, const float *__restrict__ coef, int n_t,
+                                              int b, int h, int w, float *__restrict__ x12)
 {
-    const int hw = h * w;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const int s = blockIdx.y; // ti*b + bi
+    if (p >= h * w) return;
+    const int ti = s / b, bi = s - ti * b;
+    prep_sample(i0, i1, flow, coef + ti * 6, bi, s, h, w, p, x12);
+}
+
+// tab[s] = {pair, coefficient row, output frame} (the frame is k_f32_to_u8_tab's)
+__global__ __launch_bounds__(256) void k_prep_tab(const float *__restrict__ i0, const float *__restrict__ i1,
+                                                  const float *__restrict__ flow, const float *__restrict__ coef,
+                                                  const int *__restrict__ tab, int h, int w, float *__restrict__ x12)
+{
     const int p = blockIdx.x * 256 + threadIdx.x;
     const int s = blockIdx.y;
-    if (p >= hw) return;
-    const int ti = s / b, bi = s - ti * b;
+    if (p >= h * w) return;
+    prep_sample(i0, i1, flow, coef + tab[3 * s + 1] * 6, tab[3 * s], s, h, w, p, x12);
+}
+
+// slomo.py:421-433 for sample s of pair bi at time row c
+__device__ __forceinline__ void fuse_sample(const float *__restrict__ i0, const float *__restrict__ i1,
+                                            const float *__restrict__ x12, const float *__restrict__ intrp,
+                                            const float *__restrict__ c, int bi, int s, int h, int w, int p,
+                                            float *__restrict__ out)
+{
+    const int hw = h * w;
     const float *x = x12 + (size_t)s * 12 * hw + p;
     const float *q = intrp + (size_t)s * 5 * hw + p;
     const float ft0x = q[0] + x[8 * hw], ft0y = q[hw] + x[9 * hw];
@@ -627,8 +642,31 @@ __global__ __launch_bounds__(256) void k_fuse(const float *__restrict__ i0, cons
     const int py = p / w, px = p - py * w;
     const float g0 = warp_sample(i0 + (size_t)bi * hw, h, w, (float)px + ft0x, (float)py + ft0y);
     const float g1 = warp_sample(i1 + (size_t)bi * hw, h, w, (float)px + ft1x, (float)py + ft1y);
-    const float w0 = coef[ti * 6 + 4], w1 = coef[ti * 6 + 5]; // wCoeff = [1 - t, t]
+    const float w0 = c[4], w1 = c[5]; // wCoeff = [1 - t, t]
     out[(size_t)s * hw + p] = (w0 * v0 * g0 + w1 * v1 * g1) / (w0 * v0 + w1 * v1);
+}
+
+__global__ __launch_bounds__(256) void k_fuse(const float *__restrict__ i0, const float *__restrict__ i1,
+                                              const float *__restrict__ x12, const float *__restrict__ intrp,
+                                              const float *__restrict__ coef, int n_t, int b, int h, int w,
+                                              float *__restrict__ out)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const int s = blockIdx.y;
+    if (p >= h * w) return;
+    const int ti = s / b, bi = s - ti * b;
+    fuse_sample(i0, i1, x12, intrp, coef + ti * 6, bi, s, h, w, p, out);
+}
+
+__global__ __launch_bounds__(256) void k_fuse_tab(const float *__restrict__ i0, const float *__restrict__ i1,
+                                                  const float *__restrict__ x12, const float *__restrict__ intrp,
+                                                  const float *__restrict__ coef, const int *__restrict__ tab, int h, int w,
+                                                  float *__restrict__ out)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const int s = blockIdx.y;
+    if (p >= h * w) return;
+    fuse_sample(i0, i1, x12, intrp, coef + tab[3 * s + 1] * 6, tab[3 * s], s, h, w, p, out);
 }
 
 // largest |x| of a tensor into a range slot (the network input of v2e_unet_forward)
@@ -655,11 +693,13 @@ __global__ void k_zero_u32(unsigned *__restrict__ p, int n)
 // squared speed vx*vx + vy*vy (two products and one sum, each rounded: contraction is off for this file) of both flow pairs
 // and the host takes ONE float32 sqrt of the maximum -- the same number as max(sqrt(...)) over the planes.  Non-negative floats
 // order like their bit patterns: one atomicMax per wave.
-__global__ __launch_bounds__(256) void k_max_speed2(const float *__restrict__ flow, int b, int hw, unsigned *__restrict__ out_bits)
+// one workgroup's share (workgroup `blk` of `nblk`) of the squared-speed maximum of flow [b][4][hw], into *out_bits
+__device__ __forceinline__ void max_speed2_part(const float *__restrict__ flow, int b, int hw, int blk, int nblk,
+                                                unsigned *__restrict__ out_bits)
 {
     float m = 0.f;
     const long long n = (long long)b * hw;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    for (long long i = (long long)blk * 256 + threadIdx.x; i < n; i += (long long)nblk * 256) {
         const int bi = (int)(i / hw);
         const int p = (int)(i - (long long)bi * hw);
         const float *fl = flow + (size_t)bi * 4 * hw + p;
@@ -676,6 +716,22 @@ __global__ __launch_bounds__(256) void k_max_speed2(const float *__restrict__ fl
         bits = other > bits ? other : bits;
     }
     if ((threadIdx.x & 63) == 0 && bits != 0u) atomicMax(out_bits, bits);
+}
+
+__global__ __launch_bounds__(256) void k_max_speed2(const float *__restrict__ flow, int b, int hw, unsigned *__restrict__ out_bits)
+{
+    max_speed2_part(flow, b, hw, blockIdx.x, gridDim.x, out_bits);
+}
+
+// the same per batch of `seg` pairs: blockIdx.y = batch (the last one may hold fewer pairs), one result slot each.  A maximum is
+// the same whichever workgroups fold it: bit for bit k_max_speed2 over that batch alone.
+__global__ __launch_bounds__(256) void k_max_speed2_seg(const float *__restrict__ flow, int b, int seg, int hw,
+                                                        unsigned *__restrict__ out_bits)
+{
+    const int j = blockIdx.y;
+    const int b0 = j * seg;
+    const int nb = min(seg, b - b0);
+    max_speed2_part(flow + (size_t)b0 * 4 * hw, nb, hw, blockIdx.x, gridDim.x, out_bits + j);
 }
 
 // ---------------------------------------------------------------- dispatch
@@ -1113,6 +1169,40 @@ int v2e_slomo_max_speed2(const float *flow, int b, int h, int w, uint32_t *out_b
     int blocks = v2e_cdiv(n, 256);
     if (blocks > 2048) blocks = 2048;
     k_max_speed2<<<blocks, 256, 0, s>>>(flow, b, h * w, out_bits);
+    V2E_HIP(hipGetLastError());
+    return 0;
+}
+
+int v2e_slomo_max_speed2_seg(const float *flow, int b, int seg, int h, int w, uint32_t *out_bits, void *stream)
+{
+    V2E_REQUIRE(flow && out_bits && b > 0 && seg > 0 && h > 0 && w > 0, "bad max_speed_seg args");
+    hipStream_t s = (hipStream_t)stream;
+    const int nseg = v2e_cdiv(b, seg);
+    V2E_REQUIRE(nseg <= 65535, "too many batches for one max_speed_seg launch");
+    k_zero_u32<<<v2e_cdiv(nseg, 64), 64, 0, s>>>(out_bits, nseg);
+    int blocks = v2e_cdiv((long long)seg * h * w, 256);
+    if (blocks > 2048) blocks = 2048;
+    k_max_speed2_seg<<<dim3(blocks, nseg), 256, 0, s>>>(flow, b, seg, h * w, out_bits);
+    V2E_HIP(hipGetLastError());
+    return 0;
+}
+
+int v2e_slomo_prep_tab(const float *i0, const float *i1, const float *flow, const float *tcoef, const int32_t *tab, int n,
+                       int h, int w, float *x12, void *stream)
+{
+    V2E_REQUIRE(i0 && i1 && flow && tcoef && tab && x12 && n > 0 && n <= 65535 && h > 0 && w > 0, "bad prep_tab args");
+    dim3 grid(v2e_cdiv((int64_t)h * w, 256), n);
+    k_prep_tab<<<grid, 256, 0, (hipStream_t)stream>>>(i0, i1, flow, tcoef, tab, h, w, x12);
+    V2E_HIP(hipGetLastError());
+    return 0;
+}
+
+int v2e_slomo_fuse_tab(const float *i0, const float *i1, const float *x12, const float *intrp, const float *tcoef,
+                       const int32_t *tab, int n, int h, int w, float *out, void *stream)
+{
+    V2E_REQUIRE(i0 && i1 && x12 && intrp && tcoef && tab && out && n > 0 && n <= 65535 && h > 0 && w > 0, "bad fuse_tab args");
+    dim3 grid(v2e_cdiv((int64_t)h * w, 256), n);
+    k_fuse_tab<<<grid, 256, 0, (hipStream_t)stream>>>(i0, i1, x12, intrp, tcoef, tab, h, w, out);
     V2E_HIP(hipGetLastError());
     return 0;
 }

@@ -17,6 +17,7 @@ interpTime pair + k/U (in source frame intervals), and v2e.py stretches the inte
 duration of the source clip: t = interpTime * (N_src - 1) * interval / (max(interpTimes) - min(interpTimes)).
 """
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -24,6 +25,7 @@ import torch
 from . import _capi
 from ._capi import check
 from .resample import coeffs_8bpc
+from .slomo import speed_from_bits, time_coefficients
 
 
 def _ptr(t):
@@ -58,49 +60,109 @@ class DeviceResampler:
         return out
 
 
-def interp_frame_times(n_src, U, src_frame_interval_s, batch_size=None):
-    """Times of the (n_src - 1) * U interpolated frames as v2e.py computes them, operation for operation: interpTimes are built
-    per batch of `batch_size` pairs as inputFrameCounter + k * (1 / U) (slomo.py:391-400; None: one batch), then normalised
-    to the processed duration of the source clip (v2e.py:786-797: f = srcVideoRealProcessedDuration / (max(interpTimes) -
-    min(interpTimes)); interpTimes = f * interpTimes)."""
+def interp_times(n_src, U, batch_size=None, factors=None):
+    """The un-normalised interpTimes of slomo.interpolate (slomo.py:388-400): per batch of `batch_size` pairs (None: one batch)
+    inputFrameCounter + k * (1 / U_b), k < U_b * pairs in the batch.  factors: U_b per batch (auto_upsample); None: U for all."""
     npairs = n_src - 1
     bs = npairs if not batch_size else int(batch_size)
+    starts = range(0, npairs, bs)
+    factors = [U] * len(starts) if factors is None else [int(u) for u in factors]
+    if len(factors) != len(starts):
+        raise ValueError("%d upsampling factors for %d batches" % (len(factors), len(starts)))
     parts = []
-    for b0 in range(0, npairs, bs):
+    for b0, u in zip(starts, factors):
         nb = min(bs, npairs - b0)
-        parts.append(b0 + np.array(range(U * nb)) * (1 / U))
-    interp = np.concatenate(parts)
-    duration = npairs * float(src_frame_interval_s)
+        parts.append(b0 + np.array(range(u * nb)) * (1 / u))
+    return np.concatenate(parts)
+
+
+def interp_frame_times(n_src, U, src_frame_interval_s, batch_size=None, factors=None):
+    """Times of the interpolated frames as v2e.py computes them, operation for operation: interpTimes are built per batch of
+    `batch_size` pairs as inputFrameCounter + k * (1 / U) (`interp_times`; factors: one U per batch, auto_upsample), then
+    normalised to the processed duration of the source clip (v2e.py:786-797: f = srcVideoRealProcessedDuration / (max(interpTimes) -
+    min(interpTimes)); interpTimes = f * interpTimes)."""
+    interp = interp_times(n_src, U, batch_size, factors)
+    duration = (n_src - 1) * float(src_frame_interval_s)
     f = duration / (np.max(interp) - np.min(interp))
     return f * interp
 
 
+def auto_upsampling_factor(speed_bits, minimum=None):
+    """slomo.py:352-379: a batch's upsampling factor from the float32 bits of its largest squared flow speed
+    (v2e_slomo_max_speed2): ceil of the float32 sqrt, at least `minimum` (None: no minimum) and at least 2.  A NaN flow raises
+    ValueError, as int(np.ceil(nan)) does in the reference."""
+    speed = speed_from_bits(speed_bits)
+    if speed != speed:
+        raise ValueError("auto_upsample: the flow of a batch is NaN, so its upsampling factor is undefined")
+    u = int(np.ceil(speed))
+    if minimum is not None and minimum > u:
+        u = minimum
+    if u < 2:
+        u = 2
+    return u
+
+
+def auto_sample_table(factors, n_pairs, batch_size):
+    """The samples of a flow chunk of n_pairs pairs whose batches of batch_size pairs have the upsampling factors `factors`, in v2e
+    frame order (slomo.py:441: batch offset + U_b * pair in batch + k): (ts, tab, cuts) with ts the time points (k + 0.5) / U
+    (slomo.py:405) of every distinct U, tab one (pair, row of ts, output frame) per sample, cuts the batches' first samples and the
+    end.  Every entry is checked against the sizes: the kernels index with them."""
+    if (len(factors) - 1) * batch_size >= n_pairs or len(factors) * batch_size < n_pairs:
+        raise ValueError("%d factors for %d pairs in batches of %d" % (len(factors), n_pairs, batch_size))
+    ts, row0 = [], {}
+    for u in sorted(set(factors)):
+        row0[u] = len(ts)
+        ts += [(k + 0.5) / u for k in range(u)]
+    tab, cuts = [], [0]
+    for j, u in enumerate(factors):
+        b0, b1 = j * batch_size, min((j + 1) * batch_size, n_pairs)
+        for i in range(b0, b1):
+            for k in range(u):
+                tab.append((i, row0[u] + k, cuts[-1] + u * (i - b0) + k))
+        cuts.append(len(tab))
+    n = len(tab)
+    assert all(0 <= p < n_pairs and 0 <= r < len(ts) and 0 <= f < n for p, r, f in tab)
+    return ts, tab, cuts
+
+
+# Samples per interpolation-UNet call of the auto_upsample path: consecutive batches (each with its own U_b) are packed into calls
+# of at most this many samples.  0: one call per batch (no packing; A/B runs).  DESIGN.md section 5 has the measurement.
+AUTO_SAMPLES_PER_CALL = 128
+
+
 class VideoToEvents:
     """SuperSloMo upsampling + DVS emulation of one clip without leaving HBM."""
+    auto_upsample = False  # (also for subclasses that set their own attributes instead of calling __init__)
 
-    def __init__(self, slomo_engine, emulator, upsampling_factor, batch_size=8, mean=0.428):
+    def __init__(self, slomo_engine, emulator, upsampling_factor, batch_size=8, mean=0.428, auto_upsample=False):
+        """auto_upsample=True (v2e's default mode, slomo.py:352-379): every batch of `batch_size` source pairs gets its own factor
+        U_b = max(ceil(largest flow speed of the batch), upsampling_factor or 0, 2); upsampling_factor is then the minimum and may
+        be None.  After a run: `upsampling_factors` (per batch), `interpTimes` (un-normalised, what slomo.interpolate returns) and
+        `avg_upsampling_factor`."""
         self.eng = slomo_engine
         self.emu = emulator
-        self.U = int(upsampling_factor)
+        self.auto_upsample = bool(auto_upsample)
+        if self.auto_upsample:
+            self.U = None if upsampling_factor is None else int(upsampling_factor)
+        else:
+            self.U = int(upsampling_factor)
         self.batch_size = int(batch_size)
         self.mean = float(mean)
         self.lib = _capi.lib()
         self._rs_in = self._rs_out = None
+        self.samples_per_call = int(os.environ.get("V2E_AMD_AUTO_SAMPLES_PER_CALL", AUTO_SAMPLES_PER_CALL))
+        self.upsampling_factors = self.interpTimes = self.avg_upsampling_factor = None
+        self.host_syncs = 0  # auto_upsample: factor read-backs of the last upsample() (one per flow chunk)
 
     def upsample(self, frames_u8):
         """frames_u8: device uint8 [N,H,W] -> device uint8 [(N-1)*U, H, W], the frames the reference's
-        interpolate() would have written as PNGs (in order)."""
+        interpolate() would have written as PNGs (in order).  auto_upsample: sum over batches of U_b * pairs frames."""
+        if self.auto_upsample:
+            return self._upsample_auto(frames_u8)
         dev = self.eng.device
         N, H, W = frames_u8.shape
-        dim = (int(W / 32) * 32, int(H / 32) * 32)  # (w, h), dataloader.py:122-123
-        w, h = dim
-        if self._rs_in is None or (self._rs_in.ih, self._rs_in.iw) != (H, W):
-            self._rs_in = DeviceResampler((H, W), (h, w), "lanczos", dev)
-            self._rs_out = DeviceResampler((h, w), (H, W), "bilinear", dev)
+        x, h, w = self._normalised_input(frames_u8)
         s = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        small = self._rs_in(frames_u8.contiguous())
-        x = torch.empty((N, 1, h, w), dtype=torch.float32, device=dev)
-        check(self.lib.v2e_u8_to_f32_norm(_ptr(small), _ptr(x), small.numel(), self.mean, s()), "v2e_u8_to_f32_norm")
         U = self.U
         ts = [(k + 0.5) / U for k in range(U)]
         out = torch.empty(((N - 1) * U, H, W), dtype=torch.uint8, device=dev)
@@ -120,6 +182,83 @@ class VideoToEvents:
             out[b0 * U:b1 * U] = self._rs_out(q)
         return out
 
+    def _normalised_input(self, frames_u8):
+        """LANCZOS to the network size (dataloader.py:122-123, 142) and ToTensor + Normalize: ([N,1,h,w] float32, h, w)."""
+        dev = self.eng.device
+        N, H, W = frames_u8.shape
+        dim = (int(W / 32) * 32, int(H / 32) * 32)  # (w, h), dataloader.py:122-123
+        w, h = dim
+        if self._rs_in is None or (self._rs_in.ih, self._rs_in.iw) != (H, W):
+            self._rs_in = DeviceResampler((H, W), (h, w), "lanczos", dev)
+            self._rs_out = DeviceResampler((h, w), (H, W), "bilinear", dev)
+        small = self._rs_in(frames_u8.contiguous())
+        x = torch.empty((N, 1, h, w), dtype=torch.float32, device=dev)
+        check(self.lib.v2e_u8_to_f32_norm(_ptr(small), _ptr(x), small.numel(), self.mean,
+                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "v2e_u8_to_f32_norm")
+        return x, h, w
+
+    def _upsample_auto(self, frames_u8):
+        """auto_upsample: the flow UNet runs on chunks of up to 64 pairs (whole batches); one launch gives every batch's largest
+        squared speed, read back ONCE per chunk -- behind the next chunk's flow UNet, which is enqueued first.  The chunk's samples
+        (v2e frame order: batch offset + U_b * pair + k) go through the interpolation UNet in calls of up to `samples_per_call`
+        samples that may span batches with different U_b (k_prep_tab / k_fuse_tab), and each sample is truncated straight into its
+        frame slot, so the chunk's frames are one contiguous range for the BILINEAR resize."""
+        dev = self.eng.device
+        N = int(frames_u8.shape[0])
+        P, bs = N - 1, self.batch_size
+        if P < 1:
+            raise ValueError("auto_upsample needs at least two source frames, got %d" % N)
+        x, h, w = self._normalised_input(frames_u8)
+        cur = torch.cuda.current_stream(dev)
+        s = C.c_void_p(cur.cuda_stream)
+        fc = bs * max(1, 64 // bs)  # pairs per flow-UNet call: whole interpolation batches
+        chunks = [(f0, min(f0 + fc, P)) for f0 in range(0, P, fc)]
+        bits_dev = torch.empty((fc + bs - 1) // bs, dtype=torch.int32, device=dev)
+        bits_host = torch.empty(bits_dev.shape, dtype=torch.int32, pin_memory=True)
+        factors, outs = [], []
+        self.host_syncs = 0
+        flow = self.eng.flow(x[0:chunks[0][1]], x[1:chunks[0][1] + 1])
+        for ci, (f0, f1) in enumerate(chunks):
+            nb = (f1 - f0 + bs - 1) // bs
+            self.eng.max_speed2_segments(flow, bs, bits_dev)
+            bits_host[:nb].copy_(bits_dev[:nb], non_blocking=True)
+            ready = torch.cuda.Event()
+            ready.record(cur)
+            nxt = None
+            if ci + 1 < len(chunks):  # the next chunk's flow UNet is queued before the host waits for this chunk's factors
+                g0, g1 = chunks[ci + 1]
+                nxt = self.eng.flow_net.forward(torch.cat((x[g0:g1], x[g0 + 1:g1 + 1]), dim=1).contiguous(), defer_check=True)
+            ready.synchronize()
+            self.host_syncs += 1
+            us = [auto_upsampling_factor(b, self.U) for b in bits_host[:nb].tolist()]
+            factors += us
+            outs.append(self._interpolate_chunk(x[f0:f1], x[f0 + 1:f1 + 1], flow, us, h, w, s))
+            if nxt is not None:
+                self.eng.flow_net.redo_if_flagged()
+                flow = nxt
+        self.upsampling_factors = factors
+        self.interpTimes = interp_times(N, None, bs, factors)
+        self.avg_upsampling_factor = sum(factors) / len(factors)
+        return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+    def _interpolate_chunk(self, I0, I1, flow, us, h, w, s):
+        """uint8 [sum U_b * pairs_b, H, W] of one flow chunk whose batches have the factors `us`."""
+        dev = self.eng.device
+        npairs = int(I0.shape[0])
+        ts, tab, cuts = auto_sample_table(us, npairs, self.batch_size)
+        n = len(tab)
+        coef = torch.from_numpy(time_coefficients(ts)).pin_memory().to(dev, non_blocking=True)
+        tab_dev = torch.tensor(tab, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        cap = self.samples_per_call
+        calls = [(a, min(a + cap, n)) for a in range(0, n, cap)] if cap > 0 else list(zip(cuts[:-1], cuts[1:]))
+        q = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
+        I0, I1 = I0.contiguous(), I1.contiguous()
+        for a, b in calls:
+            out = self.eng.interpolate_table(I0, I1, flow, coef, tab_dev, a, b - a)
+            check(self.lib.v2e_f32_to_u8_trunc_tab(_ptr(out), _ptr(q), _ptr(tab_dev[a:b]), b - a, h * w, self.mean, s),
+                  "v2e_f32_to_u8_trunc_tab")
+        return self._rs_out(q)
+
     def upsample_sharded(self, frames_u8, group=None, owner=None):
         """SuperSloMo of ONE clip over the ranks of `group` (BASELINE north_star: "frame batches shard across the
         GPUs"): the P = N - 1 source pairs are independent (slomo.py:330-466: every batch is computed from its own frames), so rank r
@@ -129,6 +268,9 @@ class VideoToEvents:
         Returns uint8 [(N - 1) U, H, W] on the assembling rank(s), None elsewhere.  Every rank must hold the same frames_u8 (or at
         least its own slice of it: only frames lo .. hi are read)."""
         import torch.distributed as dist
+        if self.auto_upsample:
+            raise NotImplementedError("auto_upsample: upsample_sharded needs the ranks' frame counts, which no longer follow from "
+                                      "(pairs, world size) alone")
         if group is None and not dist.is_initialized():
             return self.upsample(frames_u8)
         G, r = dist.get_world_size(group), dist.get_rank(group)
@@ -146,6 +288,15 @@ class VideoToEvents:
         and sent to the owner (point to point, exact sizes), the owner's DVS stage taking chunk c (enqueued, not waited for) while
         the ranks, the owner included, interpolate chunk c + 1: for a long clip the owner no longer idles through the whole
         interpolation and holds one chunk of frames, not the clip.  Same frames, order, times and events as one rank."""
+        if self.auto_upsample:
+            if group is not None or chunk_pairs:
+                raise NotImplementedError("auto_upsample with group= / chunk_pairs=: the ranks' frame counts would no longer follow "
+                                          "from (pairs, world size) alone, so the ranks would have to exchange block sizes")
+            up = self.upsample(frames_u8)
+            times = interp_frame_times(int(frames_u8.shape[0]), None, float(src_frame_interval_s), self.batch_size,
+                                       factors=self.upsampling_factors)
+            ev, counts = self.emu.generate_events_batch(up, times, return_device=return_device)
+            return ev, counts, int(up.shape[0])
         if group is not None and chunk_pairs:
             return self._run_chunked(frames_u8, src_frame_interval_s, return_device, group, owner, int(chunk_pairs))
         if group is not None:

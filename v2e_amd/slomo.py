@@ -216,6 +216,15 @@ class HipUNet:
         return True
 
 
+def speed_from_bits(bits):
+    """The flow speed (pixels per source frame) from the float32 bits of a squared-speed maximum (v2e_slomo_max_speed2): ONE
+    float32 sqrt, as slomo.py:359-368 takes it per plane; NaN for the NaN marker 0xffffffff."""
+    bits = int(bits) & 0xFFFFFFFF
+    if bits == 0xFFFFFFFF:
+        return float("nan")
+    return float(np.sqrt(np.array([bits], dtype=np.uint32).view(np.float32)[0]))
+
+
 def time_coefficients(ts):
     """[n_t][6] float32: fCoeff[0..3] (slomo.py:406-407) and wCoeff (:429), in Python doubles first."""
     rows = []
@@ -376,10 +385,39 @@ class SloMoEngine:
         if self._speed_bits is None:
             self._speed_bits = torch.zeros(1, dtype=torch.int32, device=self.device)
         check(self.lib.v2e_slomo_max_speed2(_ptr(flow), b, h, w, _ptr(self._speed_bits), self._stream()), "v2e_slomo_max_speed2")
-        bits = int(self._speed_bits.item()) & 0xFFFFFFFF
-        if bits == 0xFFFFFFFF:
-            return float("nan")
-        return float(np.sqrt(np.array([bits], dtype=np.uint32).view(np.float32)[0]))
+        return speed_from_bits(self._speed_bits.item())
+
+    def max_speed2_segments(self, flow, seg, out_bits):
+        """v2e_slomo_max_speed2 of every batch of `seg` pairs of a flow chunk (the last batch may be shorter) in one launch, into
+        the device int32 tensor out_bits[ceil(b / seg)] (not read back: `speed_from_bits` turns an entry into the speed)."""
+        b, c, h, w = flow.shape
+        assert c == 4 and flow.dtype == torch.float32 and flow.is_contiguous()
+        assert out_bits.dtype == torch.int32 and out_bits.device == self.device and out_bits.numel() >= (b + seg - 1) // seg
+        check(self.lib.v2e_slomo_max_speed2_seg(_ptr(flow), b, int(seg), h, w, _ptr(out_bits), self._stream()),
+              "v2e_slomo_max_speed2_seg")
+
+    def interpolate_table(self, I0, I1, flow, coef, tab, row0, n):
+        """The interpolated frames of samples row0 .. row0 + n of a ragged sample table (auto_upsample: batches with different
+        numbers of time points in ONE interpolation-UNet call): tab is a device int32 [samples][3] of {pair of I0 / I1 / flow,
+        row of coef, output frame}, coef the device float32 [rows][6] of `time_coefficients`.  Sample for sample the arithmetic
+        of `interpolate` (k_prep_tab / k_fuse_tab run k_prep / k_fuse's per-sample code).  Returns [n, 1, H, W] float32; the
+        caller has checked the table against the tensors' sizes."""
+        _, _, H, W = I0.shape
+        assert I0.is_contiguous() and I1.is_contiguous() and flow.is_contiguous() and tab.is_contiguous() and coef.is_contiguous()
+        assert I1.shape == I0.shape and tuple(flow.shape) == (I0.shape[0], 4, H, W) and coef.shape[1] == 6
+        assert tab.dtype == torch.int32 and tab.shape[1] == 3 and 0 <= row0 and 0 < n and row0 + n <= tab.shape[0]
+        t = tab[row0:row0 + n]
+        x12 = torch.empty((n, 12, H, W), dtype=torch.float32, device=self.device)
+        check(self.lib.v2e_slomo_prep_tab(_ptr(I0), _ptr(I1), _ptr(flow), _ptr(coef), _ptr(t), n, H, W, _ptr(x12), self._stream()),
+              "v2e_slomo_prep_tab")
+        out = torch.empty((n, 1, H, W), dtype=torch.float32, device=self.device)
+        intrp = self.interp_net.forward(x12, defer_check=True)
+        for _ in range(2):  # as in interpolate: the range flag is read behind the fusion
+            check(self.lib.v2e_slomo_fuse_tab(_ptr(I0), _ptr(I1), _ptr(x12), _ptr(intrp), _ptr(coef), _ptr(t), n, H, W, _ptr(out),
+                                              self._stream()), "v2e_slomo_fuse_tab")
+            if not self.interp_net.redo_if_flagged():
+                break
+        return out
 
     def interpolate(self, I0, I1, ts, flow=None, next_pair=None):
         """Ft_p for every t in ts and every pair in the batch: returns [len(ts), B, 1, H, W].
