@@ -1755,7 +1755,7 @@ static bool chain_fused_records(const v2e_emu *h, int dtype, int nD)
     return fused_env >= 0 ? fused_env != 0 : !chain_small_grid(h);
 }
 
-static size_t chain_dyn_lds(bool fused) { return fused ? 0 : (size_t)CHAIN_SUB * BLOCK * sizeof(uint2); }
+static size_t chain_dyn_lds(bool) { return 0; } // (k_chain decodes its records into registers: no dynamic LDS)
 
 // allon: every run-time feature switch of the frame loop is on (cutoff, leak, shot noise, refractory period: the v2e CLI
 // defaults) -> the instantiation without those tests; built for float64 state and uint8 frames (what that configuration has)

@@ -31,6 +31,7 @@
 //
 //   Clips (independent pixel arrays) beyond what is co-resident are walked by a loop inside the workgroup.
 #pragma once
+#include <type_traits>
 #include "pull_index.h"
 
 // lock-step frames in redo passes (see k_chain): measured round 4, break-even at best; compiled out by default (the per-frame
@@ -45,7 +46,7 @@
 
 constexpr int CHAIN_K_MAX = 64; // (a lane per frame of a launch: rule thresholds, maxima, predictions)
 constexpr int CFRAME_THREADS = 1024;
-constexpr int CHAIN_SUB = 8; // frames whose records are in LDS at a time (4 KB per frame and workgroup)
+constexpr int CHAIN_SUB = 8; // frames of a sub-pass: their records are loaded together and decoded into registers at its start
 constexpr int CHAIN_MAX_ITERS = 1024; // k_cframe keeps one total per key in LDS
 
 // exact floor(a/b) for a >= 0, b > 0: equals c10::div_floor_floating (whose fmod / re-divide /
@@ -252,11 +253,19 @@ __device__ __forceinline__ uint4 make_frame_record(const KArgs &a, FT px, const 
     return pack_frame_record(eps, L, __float_as_uint(dl), sb);
 }
 
-// k_ahead's 8-byte record (see AheadArgs) of a uint8 frame -> the 16-byte record, with the frame's dt_over_tau
+// k_ahead's 8-byte record (see AheadArgs) of a uint8 frame -> the 16-byte record, with the frame's dt_over_tau: frame_record_table's
+// values, with both table entries read whatever the switches say (no branch between the table reads of a sub-pass boundary)
 __device__ __forceinline__ uint4 decode_frame_record(const KArgs &a, uint2 r8, const float *s_lutL, const double *s_lutI, double dt_over_tau)
 {
-    double L, inten01, eps;
-    frame_record_table<uint8_t>(a, (uint8_t)(r8.y & 0xFFu), s_lutL, s_lutI, dt_over_tau, L, inten01, eps);
+    const int px = (int)(r8.y & 0xFFu);
+    const float tl = s_lutL[px];
+    const double inten01 = s_lutI[px];
+    const double L = a.log_input ? (double)px : (double)tl;
+    double eps = 0.0;
+    if (a.has_cutoff) {
+        eps = inten01 * dt_over_tau;
+        if (eps > 1.0) eps = 1.0;
+    }
     return pack_frame_record(eps, L, r8.x, r8.y >> 30);
 }
 
@@ -348,11 +357,11 @@ template <typename R> __device__ __forceinline__ R floor_div_rcp(R a, R b, R rb)
     return q;
 }
 
-// FUSED = false: the frames' records come from k_ahead through LDS (small grids: the chain is one wave per SIMD and every
-// instruction in it is latency).  FUSED = true: the chain builds each record itself (large grids: the occupancy hides
-// latencies, and the records' 16 B per pixel and frame of extra HBM traffic -- 8 written, 8 read back -- would be what bounds the run).
-// Dynamic LDS (FUSED = false): [CHAIN_SUB][BLOCK] k_ahead's 8-byte records; frame_body rebuilds the 16-byte record from one with two
-// LDS table reads and a float64 multiply that no pixel state feeds.
+// FUSED = false: the frames' records come from k_ahead (small grids: the chain is one wave per SIMD and every instruction in it
+// is latency).  FUSED = true: the chain builds each record itself (large grids: the occupancy hides latencies, and the records'
+// 16 B per pixel and frame of extra HBM traffic -- 8 written, 8 read back -- would be what bounds the run).
+// FUSED = false: a sub-pass's CHAIN_SUB 8-byte records are decoded at the sub-pass boundary, all their table reads in flight at once,
+// into what frame_body consumes (1 - eps, eps * L, leak step, shot bits: registers), so that a frame starts with the IIR.
 // ALLON: instantiation for runs with a photoreceptor cutoff, leak, shot noise AND a refractory period (the v2e CLI defaults,
 // i.e. the benchmark): the per-frame tests of those run-time switches -- a scalar compare and a branch each, in a loop whose
 // every instruction is exposed latency -- are compiled out.  ALLON = false reads the switches from KArgs.
@@ -360,12 +369,13 @@ template <typename R> __device__ __forceinline__ R floor_div_rcp(R a, R b, R rb)
 // 96 VGPRs without a spill; measured 1280x720 noisy 10.25 -> 10.5 Gev/s); the other fused ones would spill a few registers.
 template <typename R, typename FT, bool FUSED, bool ALLON = false>
 __global__ __launch_bounds__(BLOCK)
-__attribute__((amdgpu_waves_per_eu((FUSED && sizeof(R) == 8 && sizeof(FT) == 1) ? 5 : 1, 8)))
+// (FUSED = false: at least two waves per SIMD -- at most 256 VGPRs -- whatever the decoded sub-pass costs in registers: 346x260's
+//  352 workgroups must stay co-resident for the redo rendezvous, or the plan falls back to one frame per launch)
+__attribute__((amdgpu_waves_per_eu((FUSED && sizeof(R) == 8 && sizeof(FT) == 1) ? 5 : (FUSED ? 1 : 2), 8)))
 void k_chain(KArgs a_in, ChainArgs ca)
 {
     KArgs a = a_in;
     if (ALLON) { a.has_cutoff = 1; a.do_leak = 1; a.do_shot = 1; a.has_refr = 1; a.use_inten = 1; }
-    extern __shared__ uint2 s_arec[];         // [CHAIN_SUB][BLOCK] k_ahead's records of the frames in flight
     __shared__ float s_lutL[256];             // lin-log tables: FUSED builds its records with them, !FUSED decodes k_ahead's
     __shared__ double s_lutI[256];            // FUSED: and the pass's frame scalars
     __shared__ double s_dtau[FUSED ? CHAIN_K_MAX : 1], s_shot[FUSED ? CHAIN_K_MAX : 1];
@@ -404,9 +414,8 @@ void k_chain(KArgs a_in, ChainArgs ca)
     for (int clip = blockIdx.y; clip < ca.n_clips; clip += (int)gridDim.y) {
         if (clip != (int)blockIdx.y) __syncthreads(); // the LDS tables of the previous clip are no longer read
         const size_t sp = (size_t)clip * a.npx_pad + p;
-        // A pass's records go through LDS, CHAIN_SUB frames at a time, their loads in flight at once.  The next CHAIN_SUB
-        // frames' records are fetched into registers BEFORE the current ones are processed and moved to LDS after them.
-        // Every thread reads back only what it wrote: no barrier.
+        // A pass's records are loaded CHAIN_SUB frames at a time, their loads in flight at once.  The next CHAIN_SUB frames'
+        // records are fetched into registers BEFORE the current ones are processed and decoded behind them.
         // ring slot of a pass's frame k: the slot of its first frame (from the host: no division in the kernel) + k, wrapped (K <= D)
         auto wrap_slot = [&](const int sl) __attribute__((always_inline)) -> int { return sl >= ca.D ? sl - ca.D : sl; };
         // !FUSED: the ring planes through buffer resources -- the ring slot goes into the instruction's SCALAR offset, the lane's pixel
@@ -429,19 +438,35 @@ void k_chain(KArgs a_in, ChainArgs ca)
             const uint4 r = decode_frame_record(a, r8, s_lutL, s_lutI, dtau);
             return valid ? r : make_uint4(0u, 0u, 0u, 0u);
         };
+        uint2 st[CHAIN_SUB]; // !FUSED: the records of a pass's first sub-pass, as stage() loaded them
         auto stage = [&](const int sl0, const int fn) __attribute__((always_inline)) { // the first CHAIN_SUB frames of a pass (sl0: the first one's slot)
             if (FUSED) return;
-            uint2 t[CHAIN_SUB];
             int sl = sl0;
 #pragma unroll
             for (int j = 0; j < CHAIN_SUB; ++j) {
-                t[j] = make_uint2(0u, 0u);
-                if (j < fn && valid) t[j] = load_rec(sl);
+                st[j] = make_uint2(0u, 0u);
+                if (j < fn && valid) st[j] = load_rec(sl);
                 if (++sl == ca.D) sl = 0;
             }
+        };
+        // !FUSED: what frame_body consumes of the sub-pass's frame j, decoded from k_ahead's record at the sub-pass boundary: 1 - eps
+        // and eps * L (the two state-free operands of the IIR, emulator_utils.py:96; L itself where there is no cutoff), the leak
+        // step, the shot decisions as count-word bits.  The same float64 operations as inside the frame, so the same values.
+        double dq_om[CHAIN_SUB], dq_el[CHAIN_SUB];
+        float dq_dl[CHAIN_SUB];
+        uint32_t dq_sb[CHAIN_SUB];
+        auto decode_sub = [&](const uint2 *r, const int kb, const double dtau_v) __attribute__((always_inline)) {
+            if (FUSED) return;
 #pragma unroll
-            for (int j = 0; j < CHAIN_SUB; ++j)
-                if (j < fn) s_arec[(size_t)j * BLOCK + tid] = t[j];
+            for (int j = 0; j < CHAIN_SUB; ++j) { // (a frame beyond the pass decodes to values nothing reads)
+                const uint4 rc = decode_rec(r[j], dtau_v, (kb + j) & (WAVE - 1));
+                const double eps = __longlong_as_double((long long)(((unsigned long long)(rc.y & 0x3FFFFFFFu) << 32) | rc.x));
+                const double L = (double)__uint_as_float(rc.z);
+                dq_om[j] = 1.0 - eps;
+                dq_el[j] = a.has_cutoff ? eps * L : L;
+                dq_dl[j] = __uint_as_float(rc.w);
+                dq_sb[j] = (rc.y >> 5) & (CNT_SHOT_ON | CNT_SHOT_OFF);
+            }
         };
         auto fill_scalars = [&](const int fs, const int fn) __attribute__((always_inline)) { // FUSED: the pass's frame scalars
             if (!FUSED) return;
@@ -600,13 +625,16 @@ void k_chain(KArgs a_in, ChainArgs ca)
             // guard of the reciprocal floor division (below): a threshold that is not positive takes the generic path
             const bool thr_bad = !(tpd > (R)0) || !(tnd > (R)0);
             constexpr double QMAX = sizeof(R) == 8 ? 1.0e9 : 1.0e6; // quotients beyond it (and NaN) take the generic path
-            // One frame of one pixel.  k: frame of the pass; js: its slot among the CHAIN_SUB frames staged in LDS (k % CHAIN_SUB; a
-            // compile-time constant in the unrolled sub-pass); returns the frame's count word.
-            auto frame_body = [&](const int k, const int js) __attribute__((always_inline)) -> uint32_t {
+            // One frame of one pixel.  k: frame of the pass; js: its slot in the sub-pass (k % CHAIN_SUB; a compile-time constant in the
+            // unrolled sub-pass); returns the frame's count word, and its event count in magq.  LIGHT (std::true_type: !FUSED, a sub-pass
+            // with no exact and no predicted rule-on frame): no per-frame lane reads, no speculation check (the sub-pass boundary takes
+            // it from magq), no rule-on walk; only the generic-division guard branches.
+            auto frame_body = [&](auto light_c, const int k, const int js, uint32_t &magq) __attribute__((always_inline)) -> uint32_t {
+                constexpr bool LIGHT = decltype(light_c)::value;
                 const int f = fs + k;
-                const uint32_t Mon = (uint32_t)__builtin_amdgcn_readlane((int)mon_v, k);
-                uint32_t exM = own ? 0u : (uint32_t)__builtin_amdgcn_readlane((int)exact_v, k);
-                // the frame's record: eps (+ shot decisions in its two free bits), lin-log value, leak step
+                const uint32_t Mon = LIGHT ? 0u : (uint32_t)__builtin_amdgcn_readlane((int)mon_v, k);
+                uint32_t exM = (LIGHT || own) ? 0u : (uint32_t)__builtin_amdgcn_readlane((int)exact_v, k);
+                // FUSED: the frame's record: eps (+ shot decisions in its two free bits), lin-log value, leak step
                 uint4 rc = make_uint4(0u, 0u, 0u, 0u);
                 if (FUSED) {
                     FT px = (FT)0;
@@ -620,17 +648,24 @@ void k_chain(KArgs a_in, ChainArgs ca)
                     const bool even = v2e_frame_half(gf) != 0u;
                     rc = make_frame_record<FT>(a, px, s_lutL, s_lutI, s_dtau[k], s_shot[k], s_dtime[k], lk, thp, ppre, npre,
                                                even ? r_even : r_odd, even ? u_even : u_odd);
-                } else {
-                    // (decoded here, not where the boundary stages it: no pixel state feeds it, and the boundary stays a copy --
-                    //  profiles/r07_emulator_experiments.txt item 2)
-                    rc = decode_rec(s_arec[(size_t)js * BLOCK + tid], dtau_v, k);
                 }
-                const double eps = __longlong_as_double((long long)(((unsigned long long)(rc.y & 0x3FFFFFFFu) << 32) | rc.x));
-                const double L = (double)__uint_as_float(rc.z);
                 R lpn; // emulator_utils.py:96
-                if (a.has_cutoff) lpn = (R)((1.0 - eps) * (double)lp + eps * L);
-                else lpn = (R)L;
-                if (a.do_leak) b = b - (R)__uint_as_float(rc.w); // emulator_utils.py:131
+                float dl;
+                uint32_t sbw; // the shot decisions as count-word bits
+                if (FUSED) {
+                    const double eps = __longlong_as_double((long long)(((unsigned long long)(rc.y & 0x3FFFFFFFu) << 32) | rc.x));
+                    const double L = (double)__uint_as_float(rc.z);
+                    if (a.has_cutoff) lpn = (R)((1.0 - eps) * (double)lp + eps * L);
+                    else lpn = (R)L;
+                    dl = __uint_as_float(rc.w);
+                    sbw = (rc.y >> 5) & (CNT_SHOT_ON | CNT_SHOT_OFF);
+                } else {
+                    if (a.has_cutoff) lpn = (R)(dq_om[js] * (double)lp + dq_el[js]);
+                    else lpn = (R)dq_el[js];
+                    dl = dq_dl[js];
+                    sbw = dq_sb[js];
+                }
+                if (a.do_leak) b = b - (R)dl; // emulator_utils.py:131
                 // counts (emulator_utils.py:137-173): diff has one sign, one exact floor division.  floor(|diff| / theta) from the
                 // reciprocal computed once per launch: |diff| * (1 / theta) is within a few ulp of the quotient, so its floor q0 is the
                 // true floor or one off, and the remainder |diff| - q0 theta -- EXACT in one fma for such a q0 -- says which (the value
@@ -656,18 +691,19 @@ void k_chain(KArgs a_in, ChainArgs ca)
                 if (FUSED && !valid) mag = 0; // (k_ahead's records of a pixel beyond the frame are zero: no events by themselves)
                 // count word: count | sign (events only) | the record's shot decisions
                 uint32_t cw = ((uint32_t)mag & CNT_MASK) | ((mag > 0 && neg) ? CNT_NEG : 0u);
-                if (a.do_shot) cw |= (rc.y >> 5) & (CNT_SHOT_ON | CNT_SHOT_OFF);
+                if (a.do_shot) cw |= sbw;
                 if (FUSED && !valid) cw = 0u;
                 if (FUSED) {
                     if (valid) WT_STORE(&ca.cnt[((size_t)wrap_slot(fs_slot + k) * ca.n_clips + clip) * a.npx_pad + p], cw);
                 }
                 const int magv = mag;
+                magq = (uint32_t)magv;
                 // speculation check: only a wave with a lane that reaches the rule threshold says so
-                if (a.has_refr && k > (own ? -1 : last_exact) && __ballot((uint32_t)magv >= Mon) != 0ull) {
+                if (!LIGHT && a.has_refr && k > (own ? -1 : last_exact) && __ballot((uint32_t)magv >= Mon) != 0ull) {
                     const int wm = wave_max_i32(magv);
                     if (lane == 0) atomicMax(gM_dst + k, (uint32_t)wm);
                 }
-                if (V2E_CHAIN_LOCKSTEP && !own && k == lock_k) { // lock-step: every frame before this one is exact, so the published maximum is M(k)
+                if (V2E_CHAIN_LOCKSTEP && !LIGHT && !own && k == lock_k) { // lock-step: every frame before this one is exact, so the published maximum is M(k)
                     __builtin_amdgcn_s_setprio(0);
                     const bool okb = clip_barrier(ca.bar_prev + (size_t)bar_idx * ca.n_clips + clip, (unsigned)ca.ngroups, ca.bar_light != 0);
                     ++bar_idx;
@@ -685,7 +721,7 @@ void k_chain(KArgs a_in, ChainArgs ca)
                 // The rule-on walk is its own branch: nothing it loads (timestamp tables) may be live in the common path,
                 // or the common path inherits a wait for every outstanding store.
                 int fcount = magv;
-                if (exM != 0u) {
+                if (!LIGHT && exM != 0u) {
                     const FrameCtl *c = ca.ctl + (size_t)f * ca.n_clips + clip;
                     const FrameTab ftb(c, lane);
                     bool ruled = false;
@@ -711,7 +747,7 @@ void k_chain(KArgs a_in, ChainArgs ca)
                     float d = (float)fcount * (neg ? thn : thp);
                     d = neg ? -d : d;
                     const R bn = b + (R)d;
-                    const bool shot = a.do_shot && (rc.y >> 30) != 0u;
+                    const bool shot = a.do_shot && sbw != 0u;
                     b = shot ? lpn : bn;
                 }
                 lp = lpn;
@@ -732,6 +768,7 @@ void k_chain(KArgs a_in, ChainArgs ca)
                     if (++sl == ca.D) sl = 0;
                 }
             };
+            decode_sub(st, c0, dtau_v);
             fetch_next(c0 + CHAIN_SUB);
             for (int k0 = c0; k0 < fn; k0 += CHAIN_SUB) {
                 if (ck_base && k0 > c0 && valid) { // state before frame k0
@@ -745,26 +782,52 @@ void k_chain(KArgs a_in, ChainArgs ca)
                 const int slot0 = wrap_slot(fs_slot + k0);
                 // the sub-pass's count words stay in registers and go out together behind it (a store inside the frame loop would
                 // stand between the loop and the arrival of the next sub-pass's records: vector memory operations retire in order)
-                uint32_t cwq[CHAIN_SUB];
+                uint32_t cwq[CHAIN_SUB], magq[CHAIN_SUB];
 #pragma unroll
-                for (int j = 0; j < CHAIN_SUB; ++j) cwq[j] = 0u;
-                if (kend - k0 == CHAIN_SUB) { // a full sub-pass, unrolled: LDS offsets, ring slots and lane indices fold
+                for (int j = 0; j < CHAIN_SUB; ++j) cwq[j] = magq[j] = 0u;
+                // the light body: the own pass, and a redo sub-pass none of whose frames is exact or predicted rule-on (exact_v zero on
+                // its lanes: every frame is finalised without the rule, as in the own pass)
+                const bool light = !FUSED && (own || (!V2E_CHAIN_LOCKSTEP && ((__ballot(exact_v != 0u) >> k0) & 0xFFull) == 0ull));
+                // (full sub-passes unrolled: ring slots and lane indices fold)
+                if (light && kend - k0 == CHAIN_SUB) {
 #pragma unroll
-                    for (int j = 0; j < CHAIN_SUB; ++j) cwq[j] = frame_body(k0 + j, j);
+                    for (int j = 0; j < CHAIN_SUB; ++j) cwq[j] = frame_body(std::true_type{}, k0 + j, j, magq[j]);
+                } else if (light) {
+#pragma unroll
+                    for (int j = 0; j < CHAIN_SUB; ++j)
+                        if (k0 + j < kend) cwq[j] = frame_body(std::true_type{}, k0 + j, j, magq[j]);
+                } else if (kend - k0 == CHAIN_SUB) {
+#pragma unroll
+                    for (int j = 0; j < CHAIN_SUB; ++j) cwq[j] = frame_body(std::false_type{}, k0 + j, j, magq[j]);
                 } else {
 #pragma unroll
                     for (int j = 0; j < CHAIN_SUB; ++j)
-                        if (k0 + j < kend) cwq[j] = frame_body(k0 + j, j);
+                        if (k0 + j < kend) cwq[j] = frame_body(std::false_type{}, k0 + j, j, magq[j]);
                 }
                 if (!FUSED) {
                     const int rem = fn - k0 - CHAIN_SUB; // frames of the pass behind this sub-pass
-                    // (A straight-line form of this boundary for full sub-passes whose slots do not wrap -- 8 LDS writes, 8 loads, 8 stores, no
-                    // per-record test -- was built in round 6 and measured 1-2 us per launch SLOWER, A/B x 3 in one session: the tests are
-                    // scalar instructions beside vector work; profiles/r06_emulator_experiments.txt item 11.)
-                    const int nnext = min(CHAIN_SUB, rem); // frames of the next sub-pass (<= 0: none)
+                    // the next sub-pass's records, decoded: their table reads in flight together, one wait
+                    if (rem > 0) decode_sub(nx, k0 + CHAIN_SUB, dtau_v);
+                    // the light body's speculation check, for the sub-pass's frames at once: the frames after the last exact one that some
+                    // lane of the wave took to the rule threshold publish the wave's max, as the general body does per frame (one branch,
+                    // rarely taken)
+                    if (light && a.has_refr) {
+                        unsigned long long hit[CHAIN_SUB], any = 0ull;
 #pragma unroll
-                    for (int j = 0; j < CHAIN_SUB; ++j) // (every lane: a lane beyond the frame keeps zero records in LDS)
-                        if (j < nnext) s_arec[(size_t)j * BLOCK + tid] = nx[j];
+                        for (int j = 0; j < CHAIN_SUB; ++j) {
+                            const uint32_t Mon = (uint32_t)__builtin_amdgcn_readlane((int)mon_v, (k0 + j) & (WAVE - 1));
+                            hit[j] = (k0 + j < kend && k0 + j > (own ? -1 : last_exact)) ? __ballot(magq[j] >= Mon) : 0ull;
+                            any |= hit[j];
+                        }
+                        if (__builtin_expect(any != 0ull, 0)) {
+#pragma unroll
+                            for (int j = 0; j < CHAIN_SUB; ++j)
+                                if (hit[j] != 0ull) {
+                                    const int wm = wave_max_i32((int)magq[j]);
+                                    if (lane == 0) atomicMax(gM_dst + k0 + j, (uint32_t)wm);
+                                }
+                        }
+                    }
                     // the sub-pass after the next: its loads go out BEFORE this sub-pass's count words (vector memory operations
                     // retire in order; the wait above then only ever covers operations a whole sub-pass old)
                     fetch_next(k0 + 2 * CHAIN_SUB);
