@@ -56,8 +56,10 @@ def sequential(toy, frames):
     return base, ts, out
 
 
-def chain(toy, frames, K, n_groups=4, checkpoints=True, predict=True, lockstep=True):
-    """The launch sequence of enqueue_run_chain + the pass loop of k_chain, all 'workgroups' of a launch in lock step."""
+def chain(toy, frames, K, n_groups=4, checkpoints=True, predict=True, lockstep=True, trace=None):
+    """The launch sequence of enqueue_run_chain + the pass loop of k_chain, all 'workgroups' of a launch in lock step.
+    trace: a dict that gets 'passes', (launch, first disagreeing frame j, checkpoint restart c0) of every redo pass, and
+    'rows', the rule-on rows [launch][K + 1][K]."""
     F = len(frames)
     nB = (F + K - 1) // K
     nL = nB + 1                                   # + the tail launch that validates the last K frames
@@ -120,6 +122,8 @@ def chain(toy, frames, K, n_groups=4, checkpoints=True, predict=True, lockstep=T
                 rnd += 1
                 redone = True
                 c0 = (j // CHAIN_SUB) * CHAIN_SUB if checkpoints else 0
+                if trace is not None:
+                    trace.setdefault("passes", []).append((L, j, c0))
                 if c0 == 0:
                     b, t = pin[0].copy(), pin[1].copy()
                 else:
@@ -136,6 +140,8 @@ def chain(toy, frames, K, n_groups=4, checkpoints=True, predict=True, lockstep=T
         else:
             planes[(L + 1) % 2] = (base.copy(), ts.copy())
     final = planes[nL % 2]
+    if trace is not None:
+        trace["rows"] = gM
     return final[0], final[1], out, passes_total
 
 

@@ -923,6 +923,7 @@ struct v2e_emu {
     std::vector<hipEvent_t> ev_ahead, ev_chain, ev_tab;
     int ch_E = 0;                   // frames per k_ahead launch / emission batch (a multiple of ch_K)
     int last_kind = -1, last_fpl = 0, last_fpb = 0; // v2e_emu_last_pipeline
+    int ch_last_launches = 0;       // chain launches of the last run with a refractory period (their rule-on rows: v2e_emu_debug_chain_rows), 0 otherwise
     void *ch_base2 = nullptr, *ch_lp2 = nullptr; // second set of state planes (ping-pong between launches)
     float *ch_ts2 = nullptr;
     int ch_long_batches = -1;      // large grids: 64-frame emission batches (1) or max(K, 8) (0: the ring would not fit); -1: not decided yet
@@ -2623,6 +2624,7 @@ int v2e_emu_run(v2e_emu *h, const v2e_emu_params *p, const void *frames, int dty
     h->last_kind = chain ? (h->ch_fused ? 4 : 3) : 0;
     h->last_fpl = chain ? h->ch_K : 1;
     h->last_fpb = chain ? h->ch_E : 1;
+    h->ch_last_launches = (chain && p->refractory_period_s > 0) ? (n_frames + h->ch_K - 1) / h->ch_K + 1 : 0; // (chain_plan's length)
     const KArgs a = make_kargs(h, p);
     if (pipelined)
         return run_pipelined(h, p, a, frames, dtype, n_frames, t_prev, t_frame, frame_idx0, events, cap, recs_dev,
@@ -2727,16 +2729,18 @@ int v2e_emu_debug_timeline(v2e_emu *h, unsigned long long *out_host /* [ngroups]
     return 0;
 }
 
-// dev tool (not part of the public header; scripts/chain_rounds.py): the rule-on rows of the last run's chain launches,
-// [launches][K + 1 rows][n_clips][K] -- row 0 what a launch's own pass flagged, row r what the r-th redo pass on it flagged
+// dev tool (not part of the public header; scripts/chain_rounds.py, tests/test_chain_redo_gpu.py): the rule-on rows of the last
+// run's chain launches, [launches][K + 1 rows][n_clips][K] -- row 0 what a launch's own pass flagged, row r what the r-th redo pass
+// on it flagged.  *launches: the last run's launch count (0: it had no refractory chain); the buffer holds ch_launch_cap launches,
+// and those beyond the last run's were not cleared by it.
 int v2e_emu_debug_chain_rows(v2e_emu *h, uint32_t *out, size_t cap_words, int *launches, int *K)
 {
     V2E_REQUIRE(h && launches && K, "null");
-    *launches = h->ch_launch_cap; *K = h->ch_K;
-    if (!h->cur().ch_gM || !out) return 0;
+    *launches = h->ch_last_launches; *K = h->ch_K;
+    if (!h->cur().ch_gM || !out || h->ch_last_launches <= 0) return 0;
     V2E_HIP(hipSetDevice(h->device));
     V2E_HIP(hipDeviceSynchronize());
-    const size_t n = (size_t)h->ch_launch_cap * (h->ch_K + 1) * h->n_clips * h->ch_K;
+    const size_t n = (size_t)h->ch_last_launches * (h->ch_K + 1) * h->n_clips * h->ch_K;
     V2E_HIP(hipMemcpy(out, h->cur().ch_gM, sizeof(uint32_t) * std::min(n, cap_words), hipMemcpyDeviceToHost));
     return 0;
 }

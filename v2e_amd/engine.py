@@ -381,6 +381,20 @@ class EmuEngine:
                     emit_batches=nb.value, frames_per_batch=fpb.value, step_launches=nsl.value,
                     chain_launch_us=[float(us[i]) for i in range(min(nl.value, 4096))])
 
+    def debug_chain_rows(self):
+        """The rule-on rows of the last run's chain launches (v2e_emu_debug_chain_rows; blocking) as a uint32 array
+        [launches][K + 1][n_clips][K]: row 0 what a launch's own pass flagged, row r what the r-th redo pass on it flagged
+        (emu_chain.h).  None when the last run had no refractory chain."""
+        nl, K = C.c_int(), C.c_int()
+        check(self.lib.v2e_emu_debug_chain_rows(self._h, None, 0, C.byref(nl), C.byref(K)), "v2e_emu_debug_chain_rows")
+        if nl.value <= 0 or K.value <= 0:
+            return None
+        out = np.zeros((nl.value, K.value + 1, self.n_clips, K.value), dtype=np.uint32)
+        check(self.lib.v2e_emu_debug_chain_rows(self._h, out.ctypes.data_as(C.c_void_p), out.size, C.byref(nl), C.byref(K)),
+              "v2e_emu_debug_chain_rows")
+        assert out.shape[0] == nl.value and out.shape[3] == K.value
+        return out
+
     def event_writer(self):
         """'k_cpull' / 'k_cemit' / None: the event writer the handle's k_chain pipeline was given (v2e_emu_event_writer)."""
         return {1: "k_cpull", 0: "k_cemit"}.get(int(self.lib.v2e_emu_event_writer(self._h)))
