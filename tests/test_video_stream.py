@@ -1,0 +1,131 @@
+"""CPU-only: the host planning of VideoToEvents.run_stream -- chunks of source pairs aligned with the flow-UNet calls of the unchunked
+upsample, per-chunk frame times that are slices of the whole clip's times bit for bit, and the validation of the source clip."""
+import numpy as np
+import pytest
+import torch
+
+CASES = [(1, 1, None), (1, 8, 64), (30, 8, None), (30, 10, 60), (64, 8, 64), (65, 8, 64), (200, 8, 64), (257, 8, 128),
+         (1000, 8, 256), (130, 3, 63), (131, 3, 126), (77, 64, 64), (300, 100, 200), (41, 1, 64), (513, 7, 189)]
+
+
+def _upsample_flow_chunks(P, bs):
+    """The (f0, f1) of every flow-UNet call of VideoToEvents.upsample (fixed U) on P pairs, as its loop forms them."""
+    fc = bs * max(1, 64 // bs)
+    out, f1 = [], 0
+    for b0 in range(0, P, bs):
+        if b0 >= f1:
+            f0, f1 = b0, min(b0 + fc, P)
+            out.append((f0, f1))
+    return out
+
+
+@pytest.mark.parametrize("P,bs,cp", CASES)
+def test_chunks_cover_the_pairs_on_flow_chunk_boundaries(P, bs, cp):
+    from v2e_amd.pipeline import flow_chunk_pairs, last_flow_chunk, stream_chunks
+    fc = flow_chunk_pairs(bs)
+    assert fc == bs * max(1, 64 // bs) and fc > 64 - bs and fc % bs == 0
+    chunks = stream_chunks(P, bs, cp)
+    assert chunks[0][0] == 0 and chunks[-1][1] == P
+    assert all(a[1] == b[0] for a, b in zip(chunks, chunks[1:]))
+    assert all(p0 < p1 and p0 % fc == 0 for p0, p1 in chunks)
+    size = 4 * fc if cp is None else cp
+    assert all(p1 - p0 == size for p0, p1 in chunks[:-1]) and chunks[-1][1] - chunks[-1][0] <= size
+    if P <= size:
+        assert chunks == [(0, P)]
+    flow = _upsample_flow_chunks(P, bs)
+    assert last_flow_chunk(P, bs) == flow[-1]
+    # every flow call of the unchunked run lies inside one chunk, and the chunk-local calls are the same calls
+    for p0, p1 in chunks:
+        assert [(p0 + a, p0 + b) for a, b in _upsample_flow_chunks(p1 - p0, bs)] == [f for f in flow if p0 <= f[0] < p1]
+
+
+@pytest.mark.parametrize("bs,cp", [(8, 32), (8, 65), (8, 0), (8, -64), (3, 64), (10, 64), (8, 64.5), (8, True), (8, "64")])
+def test_unaligned_chunk_pairs_raise(bs, cp):
+    from v2e_amd.pipeline import stream_chunks
+    with pytest.raises((ValueError, TypeError)):
+        stream_chunks(500, bs, cp)
+
+
+def test_unaligned_chunk_pairs_raise_in_run_stream():
+    from v2e_amd.pipeline import VideoToEvents
+    for auto in (False, True):
+        pipe = VideoToEvents(None, None, 4, batch_size=8, auto_upsample=auto)
+        with pytest.raises(ValueError):
+            pipe.run_stream(np.zeros((100, 40, 70), dtype=np.uint8), 1 / 30, chunk_pairs=96)
+
+
+def _fixed_factors(P, bs, U):
+    return [U] * len(range(0, P, bs))
+
+
+@pytest.mark.parametrize("P,bs,cp", CASES)
+@pytest.mark.parametrize("U", [2, 3, 7, 10])
+def test_fixed_u_chunk_times_concatenate_to_the_clip_times(P, bs, cp, U):
+    from v2e_amd.pipeline import chunk_frame_times, interp_frame_times, stream_chunks, stream_time_scale
+    dt = 1 / 30.0
+    ref = interp_frame_times(P + 1, U, dt, bs)
+    scale = stream_time_scale(P + 1, dt, bs, U)
+    parts = [chunk_frame_times(p0, p1, bs, _fixed_factors(p1 - p0, bs, U), scale) for p0, p1 in stream_chunks(P, bs, cp)]
+    got = np.concatenate(parts)
+    assert got.shape == ref.shape and np.array_equal(got.view(np.int64), ref.view(np.int64))
+
+
+@pytest.mark.parametrize("P,bs,cp", CASES)
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_auto_chunk_times_concatenate_to_the_clip_times(P, bs, cp, seed):
+    """Random factors per batch (a short last batch wherever P is not a multiple of bs); the scale from the last factor alone."""
+    from v2e_amd.pipeline import chunk_frame_times, interp_frame_times, stream_chunks, stream_time_scale
+    rng = np.random.default_rng(seed * 1000 + P)
+    nb = len(range(0, P, bs))
+    factors = [int(u) for u in rng.integers(2, 40, size=nb)]
+    for dt in (1 / 30.0, 1 / 24.0, 0.0123):
+        ref = interp_frame_times(P + 1, None, dt, bs, factors=factors)
+        scale = stream_time_scale(P + 1, dt, bs, factors[-1])
+        parts = [chunk_frame_times(p0, p1, bs, factors[p0 // bs:(p1 + bs - 1) // bs], scale)
+                 for p0, p1 in stream_chunks(P, bs, cp)]
+        got = np.concatenate(parts)
+        assert got.shape == ref.shape and np.array_equal(got.view(np.int64), ref.view(np.int64))
+
+
+def test_time_scale_depends_on_the_last_factor():
+    from v2e_amd.pipeline import interp_frame_times, stream_time_scale
+    a = interp_frame_times(21, None, 0.1, 8, factors=[5, 5, 5])
+    b = interp_frame_times(21, None, 0.1, 8, factors=[5, 5, 9])
+    assert a[5] != b[5]
+    assert stream_time_scale(21, 0.1, 8, 5) != stream_time_scale(21, 0.1, 8, 9)
+
+
+def test_chunk_times_check_their_factors():
+    from v2e_amd.pipeline import chunk_frame_times
+    with pytest.raises(ValueError):
+        chunk_frame_times(0, 20, 8, [3, 3], 1.0)
+    with pytest.raises(ValueError):
+        chunk_frame_times(4, 20, 8, [3, 3], 1.0)
+
+
+@pytest.mark.parametrize("frames", [
+    np.zeros((5, 40, 70), dtype=np.float32),
+    np.zeros((5, 40, 70), dtype=np.int16),
+    np.zeros((5, 40, 70, 3), dtype=np.uint8),
+    np.zeros((40, 70), dtype=np.uint8),
+    np.zeros((1, 40, 70), dtype=np.uint8),
+    np.zeros((0, 40, 70), dtype=np.uint8),
+    torch.zeros((5, 40, 70), dtype=torch.float32),
+    torch.zeros((5, 1, 40, 70), dtype=torch.uint8),
+    [[[0]]],
+])
+def test_source_clip_validation(frames):
+    from v2e_amd.pipeline import VideoToEvents, stream_source_shape
+    with pytest.raises((ValueError, TypeError)):
+        stream_source_shape(frames)
+    for auto in (False, True):
+        pipe = VideoToEvents(None, None, 4, batch_size=8, auto_upsample=auto)
+        with pytest.raises((ValueError, TypeError)):
+            pipe.run_stream(frames, 1 / 30)
+
+
+def test_source_clip_shapes():
+    from v2e_amd.pipeline import stream_source_shape
+    assert stream_source_shape(np.zeros((2, 3, 4), dtype=np.uint8)) == (2, 3, 4)
+    assert stream_source_shape(torch.zeros((7, 40, 70), dtype=torch.uint8)) == (7, 40, 70)
+    assert stream_source_shape(torch.zeros((7, 70, 40), dtype=torch.uint8).transpose(1, 2)) == (7, 40, 70)

@@ -139,6 +139,14 @@ def _cleanup_at_exit(ref):
         emu.cleanup()
 
 
+def default_event_capacity(n_frames, H, W):
+    """Event rows a device-resident run of n_frames frames of H x W gets when no cap is given: 4 events per pixel and frame (the
+    reference never drops events; a run that exceeds this raises and leaves the instance unusable until reset()), bounded to
+    4 GiB of rows for very long runs."""
+    per_frame = max(4 * H * W, 1 << 16)
+    return per_frame * min(n_frames, max(64, (4 << 30) // (16 * per_frame)))
+
+
 class _PendingRun:
     """Handle of an enqueued device-resident run (EventEmulator.generate_events_batch_async)."""
 
@@ -1096,10 +1104,7 @@ class EventEmulator(object):
                                                       cs_steps_dev.data_ptr()), "v2e_emu_set_csdvs_run")
         P = self._params()
         if cap is None:
-            # 4 events per pixel and frame (the reference never drops events; a clip that exceeds this raises below and
-            # leaves the instance unusable until reset()), bounded to 4 GiB of rows for very long runs
-            per_frame = max(4 * H * W, 1 << 16)
-            cap = per_frame * min(nrun, max(64, (4 << 30) // (16 * per_frame)))
+            cap = default_event_capacity(nrun, H, W)
         # two buffer sets alternate between asynchronous runs; the synchronous call has a third of its own, so that a pending
         # handle whose result() has not been read yet is never overwritten by it
         which = 2 if _single_buffer else self.__dict__.setdefault("_async_flip", 0)

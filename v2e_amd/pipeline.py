@@ -24,6 +24,7 @@ import torch
 
 from . import _capi
 from ._capi import check
+from .emulator import default_event_capacity
 from .resample import coeffs_8bpc
 from .slomo import speed_from_bits, time_coefficients
 
@@ -69,11 +70,12 @@ def interp_times(n_src, U, batch_size=None, factors=None):
     factors = [U] * len(starts) if factors is None else [int(u) for u in factors]
     if len(factors) != len(starts):
         raise ValueError("%d upsampling factors for %d batches" % (len(factors), len(starts)))
-    parts = []
-    for b0, u in zip(starts, factors):
-        nb = min(bs, npairs - b0)
-        parts.append(b0 + np.array(range(u * nb)) * (1 / u))
-    return np.concatenate(parts)
+    return np.concatenate([_batch_interp_times(b0, u, min(bs, npairs - b0)) for b0, u in zip(starts, factors)])
+
+
+def _batch_interp_times(b0, u, nb):
+    """The interpTimes of one batch of nb pairs starting at pair b0 with factor u (slomo.py:393-398)."""
+    return b0 + np.array(range(u * nb)) * (1 / u)
 
 
 def interp_frame_times(n_src, U, src_frame_interval_s, batch_size=None, factors=None):
@@ -130,6 +132,73 @@ def auto_sample_table(factors, n_pairs, batch_size):
 AUTO_SAMPLES_PER_CALL = 128
 
 
+def flow_chunk_pairs(batch_size):
+    """Pairs per flow-UNet call of `upsample` and `_upsample_auto`: whole interpolation batches, as many as fit in 64 pairs (one at least)."""
+    return int(batch_size) * max(1, 64 // int(batch_size))
+
+
+def stream_chunks(n_pairs, batch_size, chunk_pairs=None):
+    """The chunks [(p0, p1)] of source pairs that `VideoToEvents.run_stream` takes in turn.  chunk_pairs must be a positive multiple
+    of the flow chunk (`flow_chunk_pairs`; default four of them): every flow-UNet call, interpolation call and auto_upsample sample
+    packing of a chunk is then the very call the unchunked `upsample` makes, which keeps the frames bit-identical under the conv maths
+    that scale activations per call.  A clip shorter than one chunk is one chunk."""
+    fc = flow_chunk_pairs(batch_size)
+    if chunk_pairs is None:
+        chunk_pairs = 4 * fc
+    if isinstance(chunk_pairs, bool) or int(chunk_pairs) != chunk_pairs or chunk_pairs <= 0 or int(chunk_pairs) % fc:
+        raise ValueError("chunk_pairs must be a positive multiple of the flow chunk of %d pairs (batch_size %d), got %r"
+                         % (fc, int(batch_size), chunk_pairs))
+    chunk_pairs, n_pairs = int(chunk_pairs), int(n_pairs)
+    return [(p0, min(p0 + chunk_pairs, n_pairs)) for p0 in range(0, n_pairs, chunk_pairs)]
+
+
+def last_flow_chunk(n_pairs, batch_size):
+    """The pairs (f0, n_pairs) of the clip's last flow-UNet call in `upsample` / `_upsample_auto`."""
+    fc = flow_chunk_pairs(batch_size)
+    return (int(n_pairs) - 1) // fc * fc, int(n_pairs)
+
+
+def stream_time_scale(n_src, src_frame_interval_s, batch_size, last_factor):
+    """The factor f of `interp_frame_times` (v2e.py:786-797: processed duration / (max(interpTimes) - min(interpTimes))) from the
+    factor of the clip's LAST batch alone: interpTimes rise batch after batch, so the maximum is the last batch's last time, the
+    minimum the first batch's first, 0."""
+    npairs = int(n_src) - 1
+    bs = int(batch_size)
+    b0 = (npairs - 1) // bs * bs
+    last = _batch_interp_times(b0, int(last_factor), npairs - b0)
+    duration = npairs * float(src_frame_interval_s)
+    return duration / (np.max(last) - 0.0)
+
+
+def chunk_frame_times(p0, p1, batch_size, factors, scale):
+    """Times of the interpolated frames of source pairs [p0, p1) (p0 a multiple of batch_size), `factors` the U of each of their
+    batches: the slice of `interp_frame_times` for the whole clip that belongs to them, bit for bit (`scale`: stream_time_scale)."""
+    bs = int(batch_size)
+    starts = range(p0, p1, bs)
+    if p0 % bs or len(factors) != len(starts):
+        raise ValueError("%d factors for pairs [%d, %d) in batches of %d" % (len(factors), p0, p1, bs))
+    parts = [_batch_interp_times(b0, int(u), min(bs, p1 - b0)) for b0, u in zip(starts, factors)]
+    return scale * np.concatenate(parts)
+
+
+def stream_source_shape(frames_u8):
+    """(N, H, W) of the source clip of `run_stream`: a uint8 [N,H,W] torch tensor (device or host) or numpy array, N >= 2."""
+    if torch.is_tensor(frames_u8):
+        ok = frames_u8.dtype == torch.uint8
+    elif isinstance(frames_u8, np.ndarray):
+        ok = frames_u8.dtype == np.uint8
+    else:
+        raise TypeError("frames_u8 must be a torch tensor or a numpy array, got %s" % type(frames_u8).__name__)
+    if not ok:
+        raise ValueError("frames_u8 must be uint8, got %s" % frames_u8.dtype)
+    if frames_u8.ndim != 3:
+        raise ValueError("frames_u8 must be [N,H,W], got shape %s" % (tuple(frames_u8.shape),))
+    N, H, W = (int(v) for v in frames_u8.shape)
+    if N < 2 or H < 1 or W < 1:
+        raise ValueError("frames_u8 needs at least two frames of at least one pixel, got shape %s" % ((N, H, W),))
+    return N, H, W
+
+
 class VideoToEvents:
     """SuperSloMo upsampling + DVS emulation of one clip without leaving HBM."""
     auto_upsample = False  # (also for subclasses that set their own attributes instead of calling __init__)
@@ -159,16 +228,21 @@ class VideoToEvents:
         interpolate() would have written as PNGs (in order).  auto_upsample: sum over batches of U_b * pairs frames."""
         if self.auto_upsample:
             return self._upsample_auto(frames_u8)
-        dev = self.eng.device
-        N, H, W = frames_u8.shape
         x, h, w = self._normalised_input(frames_u8)
+        return self._upsample_fixed(x, h, w, tuple(frames_u8.shape[1:]))
+
+    def _upsample_fixed(self, x, h, w, out_hw):
+        """Fixed U from the normalised input x [N,1,h,w] (`_normalised_input`): uint8 [(N-1)*U, H, W]."""
+        dev = self.eng.device
+        N = int(x.shape[0])
+        H, W = out_hw
         s = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         U = self.U
         ts = [(k + 0.5) / U for k in range(U)]
         out = torch.empty(((N - 1) * U, H, W), dtype=torch.uint8, device=dev)
         # the flow UNet sees up to 64 pairs at a time (its small levels fill the GPU only with many samples; a pair's
         # flow does not depend on what else is in the batch), the interpolation UNet U x batch_size samples
-        fc = self.batch_size * max(1, 64 // self.batch_size)  # pairs per flow-UNet call: whole interpolation batches
+        fc = flow_chunk_pairs(self.batch_size)  # pairs per flow-UNet call: whole interpolation batches
         flow, f0, f1 = None, 0, 0
         for b0 in range(0, N - 1, self.batch_size):
             b1 = min(b0 + self.batch_size, N - 1)
@@ -209,14 +283,25 @@ class VideoToEvents:
         if P < 1:
             raise ValueError("auto_upsample needs at least two source frames, got %d" % N)
         x, h, w = self._normalised_input(frames_u8)
+        self.host_syncs = 0
+        out, factors = self._upsample_auto_x(x, h, w)
+        self.upsampling_factors = factors
+        self.interpTimes = interp_times(N, None, bs, factors)
+        self.avg_upsampling_factor = sum(factors) / len(factors)
+        return out
+
+    def _upsample_auto_x(self, x, h, w):
+        """auto_upsample from the normalised input x [N,1,h,w]: (uint8 frames, the factor of every batch).  Adds its factor
+        read-backs to host_syncs."""
+        dev = self.eng.device
+        P, bs = int(x.shape[0]) - 1, self.batch_size
         cur = torch.cuda.current_stream(dev)
         s = C.c_void_p(cur.cuda_stream)
-        fc = bs * max(1, 64 // bs)  # pairs per flow-UNet call: whole interpolation batches
+        fc = flow_chunk_pairs(bs)  # pairs per flow-UNet call: whole interpolation batches
         chunks = [(f0, min(f0 + fc, P)) for f0 in range(0, P, fc)]
         bits_dev = torch.empty((fc + bs - 1) // bs, dtype=torch.int32, device=dev)
         bits_host = torch.empty(bits_dev.shape, dtype=torch.int32, pin_memory=True)
         factors, outs = [], []
-        self.host_syncs = 0
         flow = self.eng.flow(x[0:chunks[0][1]], x[1:chunks[0][1] + 1])
         for ci, (f0, f1) in enumerate(chunks):
             nb = (f1 - f0 + bs - 1) // bs
@@ -236,10 +321,7 @@ class VideoToEvents:
             if nxt is not None:
                 self.eng.flow_net.redo_if_flagged()
                 flow = nxt
-        self.upsampling_factors = factors
-        self.interpTimes = interp_times(N, None, bs, factors)
-        self.avg_upsampling_factor = sum(factors) / len(factors)
-        return outs[0] if len(outs) == 1 else torch.cat(outs)
+        return (outs[0] if len(outs) == 1 else torch.cat(outs)), factors
 
     def _interpolate_chunk(self, I0, I1, flow, us, h, w, s):
         """uint8 [sum U_b * pairs_b, H, W] of one flow chunk whose batches have the factors `us`."""
@@ -312,6 +394,137 @@ class VideoToEvents:
         ev, counts = self.emu.generate_events_batch(up, times, return_device=return_device)
         return ev, counts, n
 
+    def run_stream(self, frames_u8, src_frame_interval_s, chunk_pairs=None, on_events=None, return_device=False, cap=None):
+        """The clip through the whole pipeline in chunks of `chunk_pairs` source pairs on one GPU, with device memory bounded by the
+        chunk, not the clip; returns (events, counts_per_interpolated_frame, n_interpolated_frames) as `run` does, with the same
+        events, counts, frame order, frame times, event files and (auto_upsample) `upsampling_factors`, `interpTimes` and
+        `avg_upsampling_factor` as `run` on the same clip with the same fresh emulator.
+
+        frames_u8: uint8 [N,H,W] on the device, or on the host (torch CPU tensor or numpy array: uploaded chunk by chunk through
+        two pinned staging buffers on a copy stream).  chunk_pairs: a positive multiple of the flow chunk
+        `flow_chunk_pairs(batch_size)` (default four of them; anything else raises ValueError) -- see `stream_chunks`.
+        cap: the event-row capacity of every emulator run (None: the emulator's own sizing, `default_event_capacity`, for the
+        largest chunk so far).
+
+        The SloMo stage of chunk c + 1 (resize, normalisation, flow and interpolation UNets, truncation, resize back) runs on a side
+        stream while the emulator's run of chunk c executes; the emulator is called from the caller's current stream and waits for
+        each chunk's frames with an event.  auto_upsample: the time of every frame depends on the factor of the clip's last batch
+        (v2e.py:786-797), so the flow UNet runs on the clip's last flow chunk before the first emulator run; `host_syncs` counts
+        every factor read-back, that one included.
+
+        on_events(events, counts, frame0): called once per chunk, in frame order, with the chunk's rows (None for a chunk without
+        events on the host), its per-frame counts and the index of its first interpolated frame; nothing is accumulated and the
+        call returns (None, counts of the whole clip, n).  With return_device=True the rows are a view of one of the emulator's
+        two alternating event buffers: valid for the duration of the callback only (work the callback enqueues on the current
+        stream is ordered before the buffer is reused).  Without on_events the rows are gathered (device rows copied out of the
+        emulator's buffers) and returned as `run` returns them."""
+        N, H, W = stream_source_shape(frames_u8)
+        P, bs = N - 1, self.batch_size
+        chunks = stream_chunks(P, bs, chunk_pairs)
+        dt = float(src_frame_interval_s)
+        dev = self.eng.device
+        main = torch.cuda.current_stream(dev)
+        side = self.__dict__.get("_stream_side")
+        if side is None:  # created once: the UNets' workspaces and the resamplers' tables are used on it chunk after chunk
+            side = self._stream_side = torch.cuda.Stream(dev, priority=-1)
+        side.wait_stream(main)  # the source frames and whatever used the engine before
+        for net in (self.eng.flow_net, self.eng.interp_net):
+            if getattr(net, "_ws", None) is not None:  # (a workspace allocated on another stream, replaced on this one)
+                net._ws.record_stream(side)
+        feed = _HostFrameFeed(frames_u8, chunks, dev, side) if not (torch.is_tensor(frames_u8) and frames_u8.is_cuda) else None
+        self.host_syncs = 0
+        scale = None
+        if not self.auto_upsample:
+            scale = stream_time_scale(N, dt, bs, self.U)
+        elif len(chunks) > 1:
+            f0, f1 = last_flow_chunk(P, bs)
+            with torch.cuda.stream(side):
+                src = frames_u8[f0:f1 + 1] if feed is None else feed.upload_range(f0, f1 + 1)
+                scale = stream_time_scale(N, dt, bs, self._last_flow_chunk_factors(src)[-1])
+        factors, counts, evs, runs = [], [], [], []
+        run_cap = nfr = 0
+        d2h = None if return_device else self.__dict__.get("_stream_d2h")
+        if not return_device and d2h is None:
+            d2h = self._stream_d2h = torch.cuda.Stream(dev)
+
+        def collect():
+            pend, _, frame0 = runs.pop(0)  # (the chunk's frames go with the entry: the host has waited for the run's rows)
+            ev, cnt = pend.result()
+            if not return_device:  # on a stream of its own: the caller's stream holds the next run's chain
+                with torch.cuda.stream(d2h):
+                    ev = ev.cpu().numpy() if ev is not None and ev.shape[0] else None
+            counts.append(np.asarray(cnt))
+            if on_events is not None:
+                on_events(ev, cnt, frame0)
+            else:
+                evs.append(ev.clone() if return_device else ev)
+
+        try:
+            if feed is not None:
+                feed.start(0)
+            for ci, (p0, p1) in enumerate(chunks):
+                if len(runs) == 2:  # at most two runs in flight: the emulator's two buffer sets
+                    collect()
+                if feed is not None and ci + 1 < len(chunks):
+                    feed.start(ci + 1)
+                with torch.cuda.stream(side):
+                    src = frames_u8[p0:p1 + 1] if feed is None else feed.frames(ci)
+                    x, h, w = self._normalised_input(src)
+                    if feed is not None:
+                        feed.consumed(ci)
+                    if self.auto_upsample:
+                        up, us = self._upsample_auto_x(x, h, w)
+                        factors += us
+                    else:
+                        up, us = self._upsample_fixed(x, h, w, (H, W)), [self.U] * len(range(p0, p1, bs))
+                    del x
+                    ready = torch.cuda.Event()
+                    ready.record(side)
+                if scale is None:  # auto_upsample, one chunk: its factors are the clip's
+                    scale = stream_time_scale(N, dt, bs, us[-1])
+                times = chunk_frame_times(p0, p1, bs, us, scale)
+                if cap is None:  # the emulator's own sizing, for the largest chunk so far: its first run has one frame fewer (the
+                    #              first frame is the initial state) and a set sized for that would be regrown by the third run
+                    run_cap = max(run_cap, default_event_capacity(int(up.shape[0]), H, W))
+                main.wait_event(ready)
+                # (pipelined runs overlap run after run on streams of the emulator's, which it assigns by a probe on its first such
+                #  run; a clip of one chunk has nothing to overlap and runs as run()'s does, plain launches on the caller's stream)
+                pend = self.emu.generate_events_batch_async(up, times, return_device=True, use_graph=0,
+                                                            cap=run_cap if cap is None else cap, pipelined=len(chunks) > 1)
+                runs.append((pend, up, nfr))  # (`up` is read by the emulator's own streams: kept until the run's result)
+                nfr += int(up.shape[0])
+                del up
+            while runs:
+                collect()
+        finally:
+            main.wait_stream(side)
+        if self.auto_upsample:
+            self.upsampling_factors = factors
+            self.interpTimes = interp_times(N, None, bs, factors)
+            self.avg_upsampling_factor = sum(factors) / len(factors)
+        counts = np.concatenate(counts)
+        if on_events is not None:
+            return None, counts, nfr
+        if return_device:
+            return torch.cat(evs), counts, nfr
+        evs = [e for e in evs if e is not None]
+        return (np.concatenate(evs) if evs else None), counts, nfr
+
+    def _last_flow_chunk_factors(self, frames_u8):
+        """auto_upsample: the factors of the batches of the clip's last flow chunk, from its source frames (f0 .. P): the flow UNet
+        call and the reduction `_upsample_auto_x` makes for that chunk, read back once."""
+        dev = self.eng.device
+        bs = self.batch_size
+        x = self._normalised_input(frames_u8)[0]
+        n = int(x.shape[0]) - 1
+        flow = self.eng.flow(x[0:n], x[1:n + 1])
+        nb = (n + bs - 1) // bs
+        bits_dev = torch.empty(nb, dtype=torch.int32, device=dev)
+        self.eng.max_speed2_segments(flow, bs, bits_dev)
+        bits = bits_dev.cpu().tolist()
+        self.host_syncs += 1
+        return [auto_upsampling_factor(b, self.U) for b in bits]
+
     def _run_chunked(self, frames_u8, src_frame_interval_s, return_device, group, owner, chunk_pairs):
         import torch.distributed as dist
         G, r = dist.get_world_size(group), dist.get_rank(group)
@@ -371,6 +584,54 @@ class VideoToEvents:
         else:
             ev = np.concatenate(evs)
         return ev, np.concatenate([np.asarray(c) for c in counts]), n
+
+
+class _HostFrameFeed:
+    """Source frames on the host for `VideoToEvents.run_stream`: chunk c's frames p0 .. p1 go to the device through one of two
+    pinned staging buffers on a copy stream while the chunk before is processed; the device buffer of a chunk is overwritten only
+    after the side stream has consumed it."""
+
+    def __init__(self, frames, chunks, device, side):
+        self.src = frames.numpy() if torch.is_tensor(frames) else frames
+        self.chunks, self.side = chunks, side
+        n = max(p1 - p0 + 1 for p0, p1 in chunks)
+        shape = (n,) + tuple(self.src.shape[1:])
+        self.copy = torch.cuda.Stream(device)
+        self.pinned = [torch.empty(shape, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        with torch.cuda.stream(side):  # (owned by the stream that reads them: freed behind its last use)
+            self.dev = [torch.empty(shape, dtype=torch.uint8, device=device) for _ in range(2)]
+        self.copied, self.used = [None, None], [None, None]
+
+    def start(self, ci):
+        """Enqueue the upload of chunk ci's frames."""
+        p0, p1 = self.chunks[ci]
+        k, n = ci % 2, p1 - p0 + 1
+        if self.copied[k] is not None:
+            self.copied[k].synchronize()  # the pinned buffer's last upload has left it
+        np.copyto(self.pinned[k][:n].numpy(), self.src[p0:p1 + 1])
+        if self.used[k] is not None:
+            self.copy.wait_event(self.used[k])
+        with torch.cuda.stream(self.copy):
+            self.dev[k][:n].copy_(self.pinned[k][:n], non_blocking=True)
+        self.copied[k] = torch.cuda.Event()
+        self.copied[k].record(self.copy)
+
+    def frames(self, ci):
+        """Chunk ci's frames on the device, the current (side) stream ordered behind their upload."""
+        p0, p1 = self.chunks[ci]
+        k = ci % 2
+        torch.cuda.current_stream(self.dev[k].device).wait_event(self.copied[k])
+        return self.dev[k][:p1 - p0 + 1]
+
+    def consumed(self, ci):
+        """The current stream has enqueued the last read of chunk ci's device frames."""
+        k = ci % 2
+        self.used[k] = torch.cuda.Event()
+        self.used[k].record(torch.cuda.current_stream(self.dev[k].device))
+
+    def upload_range(self, a, b):
+        """Frames a .. b - 1 on the device (one-off, on the current stream)."""
+        return torch.from_numpy(np.ascontiguousarray(self.src[a:b])).to(self.dev[0].device)
 
 
 def pair_shard(n_pairs, world, rank):
