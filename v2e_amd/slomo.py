@@ -62,6 +62,16 @@ _LOOKAHEAD = os.environ.get("V2E_AMD_SLOMO_LOOKAHEAD", "1") != "0"
 _CANARY = {}
 
 
+def weight_scale_log2(wmax):
+    """The exponent a two-float16-piece layer's weights are packed times 2^ of (v2e_pack_conv_weight_h2, ConvDesc.split_kind >> 8):
+    the exact power of two that puts the layer's largest weight `wmax` in [2^12, 2^13) -- no piece of a weight that matters is a
+    float16 subnormal, nothing overflows (65504) -- kept within 0 .. 40 (v2e_amd/csrc/slomo.hip act_scale: the convolution's
+    epilogue divides it out again together with the activations' power of two, in one exact multiply)."""
+    if not wmax > 0.0:
+        return 0
+    return max(0, min(40, 12 - math.frexp(wmax)[1] + 1))
+
+
 class HipUNet:
     """One UNet's weights, repacked [Cin][k][k][Cout] in HBM, and its forward pass."""
 
@@ -109,7 +119,7 @@ class HipUNet:
                         raise ValueError("conv_math='fp16x2': layer %s has a weight of magnitude %g, beyond float16" % (name, wmax))
                     fast_ok = False
                 else:
-                    sl2 = 0 if not wmax > 0.0 else max(0, min(40, 12 - math.frexp(wmax)[1] + 1))
+                    sl2 = weight_scale_log2(wmax)
                     w2 = torch.empty((ci + 15) // 16 * 16 * kh * kw * co * 4, dtype=torch.uint8, device=self.device)
                     check(self.lib.v2e_pack_conv_weight_h2(_ptr(w), _ptr(w2), co, ci, kh, sl2, stream), "v2e_pack_conv_weight_h2")
                     self._keep.append(w2)
@@ -162,6 +172,32 @@ class HipUNet:
         if not defer_check:
             self.redo_if_flagged()
         return out
+
+    def workspace_tensors(self, n, h, w):
+        """Read-only views of what the last forward pass of an [n, cin, h, w] input left in the workspace, by the layout of
+        v2e_unet_forward (csrc/slomo.hip: s1 s2 s3 s4 s5 | tA tB tU | range slots): the skip tensors "s1" .. "s5" (the outputs of
+        conv2 and down1 .. down4.conv2) and the two trunk tensors no later layer overwrote, "tA" (up5.conv1) and "tB" (up5.conv2).
+        For tests and diagnosis; the views alias the workspace and change with the next pass."""
+        hw = h * w
+        f = self._ws[:int(self.lib.v2e_unet_workspace_bytes(n, h, w, self.cin))].view(torch.float32)
+        out, off = {}, 0
+        for k, c in enumerate((32, 64, 128, 256, 512)):
+            hh, ww = h >> k, w >> k
+            out["s%d" % (k + 1)] = f[off:off + n * c * hh * ww].view(n, c, hh, ww)
+            off += n * c * hh * ww
+        for name in ("tA", "tB"):
+            out[name] = f[off:off + n * 32 * hw].view(n, 32, h, w)
+            off += n * 32 * hw
+        return out
+
+    def range_slots(self, n, h, w):
+        """The 32 range slots of the last forward pass of an [n, cin, h, w] input, as uint32 (float32 bit patterns): [0] the largest
+        |input|, [1 + i] the largest |output| of convolution i (UNET_LAYERS order).  Written only while some layer runs on two
+        float16 pieces (conv_math 'auto' / 'fp16x2'); the last convolution's slot has no reader, and the 4- / 5-channel conv3 kernel
+        does not write it."""
+        off = n * h * w * (32 + 16 + 8 + 4 + 2 + 32 + 32 + 64) * 4
+        torch.cuda.synchronize(self.device)
+        return self._ws[off:off + 128].cpu().numpy().view(np.uint32).copy()
 
     def walk_layers(self, x, inputs_from=None):
         """The UNet layer by layer through v2e_conv2d_lrelu (model.py:198-226: avg_pool2d and the bilinear x2 fused into the consuming
