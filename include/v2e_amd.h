@@ -524,6 +524,44 @@ int v2e_render_packet(const float *events, int64_t n_used, int mode, const doubl
                       double *frames_out, double *cur_out, int bins_y, int bins_x, double y_lo, double y_hi, double x_lo,
                       double x_hi, double full_scale, void *stream);
 
+/* EventRenderer.render_run: a whole device-resident run in one pass (v2e_amd/csrc/render.hip).  The run is events[n_rows][4]
+ * plus a packet table pkt_off[0..n_packets] (device int64, strictly increasing from 0: packet p = rows [pkt_off[p],
+ * pkt_off[p + 1]), the packets v2e.py:837-850 hands render_events_to_frames); every packet is rendered as the reference
+ * renders it on its own (renderer.py:271 resets the running frame, :296-306 leaves the packet's last event out, the frame a
+ * packet ends in is not emitted), its complete frames numbered across the run from pkt_frame0[p] on (device int32
+ * [n_packets + 1], the last entry the run's total).
+ * v2e_render_run_windows: DURATION (renderer.py:207-213, 314-318).  One lane walks the packets in order, advancing the frame
+ * start time with separate additions -- float32 additions of (float)interval if f32_time (numpy >= 2 keeps the time stamp's
+ * float32 through `+= frameIntevalS`), float64 ones otherwise -- while the packet's second-to-last time stamp lies past the next
+ * frame's start.  time_state: device double[3], {currentFrameStartTime, 1.0 once it is set}, carried from run to run and written
+ * only if commit, and [2] = the start time after this run, written always (the host's copy).  Writes pkt_frame0, packet p's start times T_0 .. T_m to bounds[pkt_frame0[p] + p ...] (needs total +
+ * n_packets entries) and every complete frame's time, the start after the increment plus interval / 2 (renderer.py:350), to
+ * frame_times; both may be null with a capacity of 0 (the counting pass).  out2[0] = complete frames, out2[1] = 1: the interval
+ * does not advance the time, 2: more than max_frames frames. */
+int v2e_render_run_windows(const float *events, const int64_t *pkt_off, int n_packets, double interval, int f32_time,
+                           double *time_state, int commit, int32_t *pkt_frame0, double *bounds, int64_t cap_bounds,
+                           double *frame_times, int64_t cap_times, int64_t max_frames, int32_t *out2, void *stream);
+/* v2e_render_run_area_segments: v2e_render_area_segments over all packets of the run in one launch (renderer.py:253-266,
+ * 292-298), area_counts carried across the packets; seg_end[pkt_frame0[p] + k] = end (exclusive, within packet p) of its
+ * complete window k, out2[0] = complete windows of the run (more than cap: seg_end was too small), out2[1] as above for the
+ * last packet. */
+int v2e_render_run_area_segments(const float *events, const int64_t *pkt_off, int n_packets, int32_t *area_counts, int nw, int nh,
+                                 double area_dimension, int area_count, int32_t *seg_end, int64_t cap, int32_t *pkt_frame0,
+                                 int32_t *out2, void *stream);
+/* v2e_render_run_frame_times: the time of every complete frame (renderer.py:343-349) -- mode 4 SOURCE: the packet's ts[0];
+ * 2 COUNT, 3 AREA_COUNT: (ts[start] + ts[end]) / 2 of the frame's window, a float32 sum -- as float64 [n_frames]. */
+int v2e_render_run_frame_times(const float *events, const int64_t *pkt_off, int n_packets, int mode, int64_t count_per_frame,
+                               const int32_t *seg_end, const int32_t *pkt_frame0, int n_frames, double *frame_times, void *stream);
+/* v2e_render_run: one histogram launch for the run -- every event finds its packet (binary search over pkt_off), its window
+ * by v2e_render_packet's rule and adds +-1 to the int32 plane of its global frame -- and one launch that clips and normalises:
+ * frames_out float64 [n_complete][bins_y][bins_x] in 0..1, or frames_u8_out, the bytes (img * 255).astype(uint8) the reference
+ * hands its AVI writer (renderer.py:339); cur_out (if has_open) = the clipped frame the LAST packet ends in.  want_frames 0:
+ * only cur_out.  diff: device int32 scratch [(want_frames ? n_complete : 0) + has_open][bins_y * bins_x]. */
+int v2e_render_run(const float *events, int64_t n_rows, const int64_t *pkt_off, int n_packets, int mode, const double *bounds,
+                   int64_t count_per_frame, const int32_t *seg_end, const int32_t *pkt_frame0, int n_complete, int has_open,
+                   int want_frames, int32_t *diff, double *frames_out, uint8_t *frames_u8_out, double *cur_out, int bins_y,
+                   int bins_x, double y_lo, double y_hi, double x_lo, double x_hi, double full_scale, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

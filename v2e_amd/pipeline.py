@@ -222,6 +222,7 @@ class VideoToEvents:
         self.samples_per_call = int(os.environ.get("V2E_AMD_AUTO_SAMPLES_PER_CALL", AUTO_SAMPLES_PER_CALL))
         self.upsampling_factors = self.interpTimes = self.avg_upsampling_factor = None
         self.host_syncs = 0  # auto_upsample: factor read-backs of the last upsample() (one per flow chunk)
+        self.dvs_frames = self.dvs_frame_times = None  # run / run_stream with renderer=: the DVS video of the last clip
 
     def upsample(self, frames_u8):
         """frames_u8: device uint8 [N,H,W] -> device uint8 [(N-1)*U, H, W], the frames the reference's
@@ -361,8 +362,26 @@ class VideoToEvents:
         mine = self.upsample(frames_u8[lo:hi + 1]) if hi > lo else frames_u8.new_empty((0,) + tuple(frames_u8.shape[1:]))
         return gather_frames_in_order(mine, N - 1, self.U, group, owner)
 
-    def run(self, frames_u8, src_frame_interval_s, return_device=False, group=None, owner=0, chunk_pairs=None):
+    def _render_hw(self, H, W):
+        """Size of the DVS video frames: the emulator's output size where it has one (v2e.py's output_height / output_width)."""
+        return int(getattr(self.emu, "output_height", None) or H), int(getattr(self.emu, "output_width", None) or W)
+
+    def _render_clip(self, renderer, ev, counts, hw, as_u8):
+        """The DVS video of a whole clip from its device rows: render_run + flush_run; leaves dvs_frames / dvs_frame_times."""
+        parts = [renderer.render_run(ev, counts, hw[0], hw[1], frame0=0, batch_size=self.batch_size, as_u8=as_u8),
+                 renderer.flush_run(hw[0], hw[1], as_u8=as_u8)]
+        parts = [p for p in parts if p[0] is not None]
+        self.dvs_frames = torch.cat([p[0] for p in parts]) if parts else None
+        self.dvs_frame_times = torch.cat([p[1] for p in parts]) if parts else None
+
+    def run(self, frames_u8, src_frame_interval_s, return_device=False, group=None, owner=0, chunk_pairs=None, renderer=None,
+            dvs_u8=False):
         """Full pipeline; returns (events, counts_per_interpolated_frame, n_interpolated_frames).
+        renderer: a v2e_amd.EventRenderer -- the clip's DVS video (v2e.py:829-850: a packet per `batch_size` emulator frames,
+        the leftover events at the end) is rendered from the device rows in one pass (EventRenderer.render_run / flush_run) and
+        left in `dvs_frames` (device float64 [m,h,w] in 0..1, or uint8 with dvs_u8; None if no frame was completed) and
+        `dvs_frame_times` (device float64 [m]; `renderer.frame_times_text` formats the reference's listing); events and counts
+        are what they are without it.  Not with group=.
         group: a torch.distributed process group -- the SuperSloMo stage is sharded over its ranks by source pairs
         (`upsample_sharded`), the frames are funnelled in order to rank `owner` (rank within the group), which holds the emulator
         state and runs the DVS model; the other ranks return (None, None, n).
@@ -370,6 +389,8 @@ class VideoToEvents:
         and sent to the owner (point to point, exact sizes), the owner's DVS stage taking chunk c (enqueued, not waited for) while
         the ranks, the owner included, interpolate chunk c + 1: for a long clip the owner no longer idles through the whole
         interpolation and holds one chunk of frames, not the clip.  Same frames, order, times and events as one rank."""
+        if renderer is not None and group is not None:
+            raise NotImplementedError("renderer= with group=: multi-rank rendering is not implemented")
         if self.auto_upsample:
             if group is not None or chunk_pairs:
                 raise NotImplementedError("auto_upsample with group= / chunk_pairs=: the ranks' frame counts would no longer follow "
@@ -377,8 +398,7 @@ class VideoToEvents:
             up = self.upsample(frames_u8)
             times = interp_frame_times(int(frames_u8.shape[0]), None, float(src_frame_interval_s), self.batch_size,
                                        factors=self.upsampling_factors)
-            ev, counts = self.emu.generate_events_batch(up, times, return_device=return_device)
-            return ev, counts, int(up.shape[0])
+            return self._emulate(up, times, return_device, renderer, dvs_u8) + (int(up.shape[0]),)
         if group is not None and chunk_pairs:
             return self._run_chunked(frames_u8, src_frame_interval_s, return_device, group, owner, int(chunk_pairs))
         if group is not None:
@@ -391,10 +411,21 @@ class VideoToEvents:
             up = self.upsample(frames_u8)
             n = up.shape[0]
         times = interp_frame_times(int(frames_u8.shape[0]), self.U, float(src_frame_interval_s), self.batch_size)
-        ev, counts = self.emu.generate_events_batch(up, times, return_device=return_device)
-        return ev, counts, n
+        return self._emulate(up, times, return_device, renderer, dvs_u8) + (n,)
 
-    def run_stream(self, frames_u8, src_frame_interval_s, chunk_pairs=None, on_events=None, return_device=False, cap=None):
+    def _emulate(self, up, times, return_device, renderer, dvs_u8):
+        """(events, counts) of the clip's interpolated frames; with a renderer the rows stay on the device until the DVS video
+        is enqueued, and go to the host (if asked for there) as generate_events_batch would have sent them."""
+        if renderer is None:
+            return self.emu.generate_events_batch(up, times, return_device=return_device)
+        ev, counts = self.emu.generate_events_batch(up, times, return_device=True)
+        self._render_clip(renderer, ev, counts, self._render_hw(int(up.shape[1]), int(up.shape[2])), dvs_u8)
+        if not return_device:
+            ev = ev.cpu().numpy() if ev is not None and ev.shape[0] else None
+        return ev, counts
+
+    def run_stream(self, frames_u8, src_frame_interval_s, chunk_pairs=None, on_events=None, return_device=False, cap=None,
+                   renderer=None, on_dvs_frames=None, dvs_u8=False):
         """The clip through the whole pipeline in chunks of `chunk_pairs` source pairs on one GPU, with device memory bounded by the
         chunk, not the clip; returns (events, counts_per_interpolated_frame, n_interpolated_frames) as `run` does, with the same
         events, counts, frame order, frame times, event files and (auto_upsample) `upsampling_factors`, `interpTimes` and
@@ -417,7 +448,16 @@ class VideoToEvents:
         call returns (None, counts of the whole clip, n).  With return_device=True the rows are a view of one of the emulator's
         two alternating event buffers: valid for the duration of the callback only (work the callback enqueues on the current
         stream is ordered before the buffer is reused).  Without on_events the rows are gathered (device rows copied out of the
-        emulator's buffers) and returned as `run` returns them."""
+        emulator's buffers) and returned as `run` returns them.
+
+        renderer: a v2e_amd.EventRenderer -- every chunk's DVS frames (EventRenderer.render_run with the chunk's first frame
+        index, so the packets are the clip's, whatever the chunking) are rendered behind that chunk's result() on a stream of
+        their own, which the emulator's runs do not wait for until they reuse the chunk's row buffer; the leftover events are
+        flushed at the end.  on_dvs_frames(frames, frame_times, first_frame_index): called in order for every chunk (and the
+        flush) that completed frames, device tensors as `render_run` returns them (uint8 frames with dvs_u8), with the render
+        stream current; without it the frames are gathered on the device and left in `dvs_frames` / `dvs_frame_times` as
+        `run` leaves them.  The renderer's read-backs (one per chunk in DURATION and AREA_COUNT mode) are added to
+        `host_syncs`.  Events, counts and event files are what they are without a renderer."""
         N, H, W = stream_source_shape(frames_u8)
         P, bs = N - 1, self.batch_size
         chunks = stream_chunks(P, bs, chunk_pairs)
@@ -447,9 +487,39 @@ class VideoToEvents:
         if not return_device and d2h is None:
             d2h = self._stream_d2h = torch.cuda.Stream(dev)
 
+        rend = self.__dict__.get("_stream_render") if renderer is not None else None
+        if renderer is not None and rend is None:
+            rend = self._stream_render = torch.cuda.Stream(dev)
+        hw = self._render_hw(H, W)
+        dvs, dvs_t, syncs0 = [], [], (renderer.host_syncs if renderer is not None else 0)
+        self.dvs_frames = self.dvs_frame_times = None
+
+        def deliver(fr, t):
+            if fr is None:
+                return
+            if on_dvs_frames is not None:
+                on_dvs_frames(fr, t, renderer.numFramesWritten - int(t.shape[0]))
+            else:
+                dvs.append(fr)
+                dvs_t.append(t)
+
+        def render(ev, cnt, frame0):
+            # the run's rows are final (result() has waited for them); they are read on the render stream, and the caller's
+            # stream -- which carries the runs that will reuse this row buffer -- is ordered behind that read.  This relies on
+            # what on_events' contract relies on: the emulator's own (pipelined) streams order every write to a row buffer behind
+            # the caller's stream at the time the run is enqueued, so work put into the caller's stream before that enqueue
+            # precedes the reuse.  COUNT and SOURCE make no read-back, so this wait is the only order there is.
+            with torch.cuda.stream(rend):
+                deliver(*renderer.render_run(ev, cnt, hw[0], hw[1], frame0=frame0, batch_size=bs, as_u8=dvs_u8))
+                read = torch.cuda.Event()
+                read.record(rend)
+            main.wait_event(read)
+
         def collect():
             pend, _, frame0 = runs.pop(0)  # (the chunk's frames go with the entry: the host has waited for the run's rows)
             ev, cnt = pend.result()
+            if renderer is not None:
+                render(ev, cnt, frame0)
             if not return_device:  # on a stream of its own: the caller's stream holds the next run's chain
                 with torch.cuda.stream(d2h):
                     ev = ev.cpu().numpy() if ev is not None and ev.shape[0] else None
@@ -496,8 +566,18 @@ class VideoToEvents:
                 del up
             while runs:
                 collect()
+            if renderer is not None:
+                with torch.cuda.stream(rend):
+                    deliver(*renderer.flush_run(hw[0], hw[1], as_u8=dvs_u8))
+                    if dvs:
+                        self.dvs_frames, self.dvs_frame_times = torch.cat(dvs), torch.cat(dvs_t)
+                        self.dvs_frames.record_stream(main)
+                        self.dvs_frame_times.record_stream(main)
+                self.host_syncs += renderer.host_syncs - syncs0
         finally:
             main.wait_stream(side)
+            if rend is not None:
+                main.wait_stream(rend)
         if self.auto_upsample:
             self.upsampling_factors = factors
             self.interpTimes = interp_times(N, None, bs, factors)
