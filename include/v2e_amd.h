@@ -137,6 +137,29 @@ int v2e_emu_set_model_state_planes(v2e_emu *h, double *log_new_frame, double *c_
 
 int v2e_emu_set_pnoise(v2e_emu *h, void *pn_arr, const float *randn_tape);
 
+/* Single-pixel model states inside v2e_emu_run (emulator.py:985-1009 per frame, the recorder behind --record_single_pixel_states,
+ * emulator.py:279-300; plotted by scripts/plot_single_pixel_states.py): the NEXT v2e_emu_run records, for each of n probed pixels
+ * (pixel_index: host array, row * W + col, the reference's plane[row, col]; the same pixel may be named twice) and each of its
+ * frames, the reference's ten series minus `time`, which the host knows, as float64 out_dev[n_frames][n][V2E_PROBE_FIELDS] in the
+ * order
+ *   0 new_frame        the frame's input value at the pixel                                            (emulator.py:988)
+ *   1 base_log_frame   after the frame's base update (emulator.py:936-942)                             (:989)
+ *   2 lp_log_frame                                                                                     (:990)
+ *   3 log_new_frame    the float32 value lin_log returns (emulator_utils.py:45)                        (:991)
+ *   4 pos_thres, 5 neg_thres   the pixel's thresholds, or the scalars when params.scalar_thres         (:992-995)
+ *   6 diff_frame       emulator.py:749-754                                                             (:996)
+ *   7 final_neg_evts_frame, 8 final_pos_evts_frame   the frame's SIGNAL events at the pixel, OFF and ON (:997-998)
+ * out_dev is device memory of the caller that holds the next run's n_frames blocks; the run writes every element and does not clear
+ * or read it.  The setting is consumed by that run (one shot: a later run is unprobed unless the call is made again); n == 0 cancels
+ * it.  n <= V2E_PROBE_MAX, every index in [0, H * W), handles of one clip only.  A probed run goes through the per-frame kernels
+ * (v2e_emu_last_pipeline reports kind 0; with V2E_RUN_REQUIRE_CHAIN it fails), never pipelined, with three small launches beside
+ * them: a tap behind k_count and one behind k_emit of every frame, and one pass over the run's event rows at the end.  The run
+ * keeps the model-state planes on (v2e_emu_set_model_state_planes; planes of the library's own where the caller has bound none).
+ * A run without probes launches nothing of this. */
+#define V2E_PROBE_FIELDS 9
+#define V2E_PROBE_MAX 64
+int v2e_emu_set_probes(v2e_emu *h, const int32_t *pixel_index, int n, double *out_dev);
+
 /* Centre-surround DVS (cs_lambda_pixels; emulator.py:245-272, 707-716, 753-754, 1061-1124).  The surround plane
  * cs_surround_frame [n_clips][npx_pad] (state dtype, caller-owned) is what v2e_emu_count subtracts from the photoreceptor
  * output: diff = (photoreceptor + noise - surround) - base; NULL switches the feature off.  Per frame the caller

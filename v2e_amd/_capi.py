@@ -20,6 +20,11 @@ RUN_ONE_FRAME_PER_LAUNCH = 128
 RUN_REQUIRE_CHAIN = 256
 RUN_PIPELINED = 1024
 RUN_FRAMES_RESIDENT = 2048
+# v2e_emu_set_probes (V2E_PROBE_* in include/v2e_amd.h): float64 fields per probe and frame, in this order, and the most probes of a run
+PROBE_FIELDS = 9
+PROBE_MAX = 64
+PROBE_FIELD_NAMES = ("new_frame", "base_log_frame", "lp_log_frame", "log_new_frame", "pos_thres", "neg_thres", "diff_frame",
+                     "final_neg_evts_frame", "final_pos_evts_frame")
 
 
 class EmuParams(C.Structure):
@@ -90,6 +95,7 @@ SIGNATURES = {
     "v2e_emu_init_state": (_i, [_vp, _PP, _vp, _i, _d, _vp, _vp, _vp, _vp]),
     "v2e_emu_set_pnoise": (_i, [_vp, _vp, _vp]),
     "v2e_emu_set_model_state_planes": (_i, [_vp, _vp, _vp, _vp]),
+    "v2e_emu_set_probes": (_i, [_vp, C.POINTER(C.c_int32), _i, _vp]),
     "v2e_emu_set_scidvs": (_i, [_vp, _vp, _vp, _vp, _u32]),
     "v2e_emu_frame_host_rows": (_i, [_vp, _vp, _u64]),
     "v2e_emu_set_csdvs": (_i, [_vp, _vp]),

@@ -857,6 +857,13 @@ struct v2e_emu {
     float *sc_tau = nullptr;
     uint32_t sc_first_frame = 0;
     double *dbg_lognew = nullptr, *dbg_cms = nullptr, *dbg_diff = nullptr; // v2e_emu_set_model_state_planes
+    // v2e_emu_set_probes: what the next run records (probe_next: consumed by v2e_emu_run into probe_run, the run being enqueued),
+    // model-state planes of the library's own for callers that bound none, the row pass's counters [n_frames][P][2] + ticket
+    V2EProbeSet probe_next = {0, {0}}, probe_run = {0, {0}};
+    double *probe_next_out = nullptr, *probe_out = nullptr;
+    double *probe_planes = nullptr;
+    unsigned int *probe_cnt = nullptr;
+    size_t probe_cnt_cap = 0;
     int ngroups = 0;
     float *lut_L = nullptr;
     double *lut_I = nullptr;
@@ -1138,6 +1145,7 @@ int v2e_emu_destroy(v2e_emu *h)
     for (hipEvent_t e : h->ev_join) hipEventDestroy(e);
     if (h->side) hipStreamDestroy(h->side);
     hipFree(h->ch_ck); hipFree(h->csr_slots);
+    hipFree(h->probe_planes); hipFree(h->probe_cnt);
     for (hipEvent_t e : h->ev_ahead) hipEventDestroy(e);
     for (hipEvent_t e : h->ev_chain) hipEventDestroy(e);
     for (hipEvent_t e : h->ev_tab) hipEventDestroy(e);
@@ -1297,6 +1305,37 @@ int v2e_emu_set_model_state_planes(v2e_emu *h, double *log_new_frame, double *c_
     V2E_REQUIRE((log_new_frame && c_minus_s_frame && diff_frame) || (!log_new_frame && !c_minus_s_frame && !diff_frame),
                 "model-state planes: all three or none");
     h->dbg_lognew = log_new_frame; h->dbg_cms = c_minus_s_frame; h->dbg_diff = diff_frame;
+    return 0;
+}
+
+int v2e_emu_set_probes(v2e_emu *h, const int32_t *pixel_index, int n, double *out_dev)
+{
+    V2E_REQUIRE(h, "null handle");
+    h->probe_next.n = 0; h->probe_next_out = nullptr;
+    if (n == 0) return 0;
+    V2E_REQUIRE(n > 0 && n <= V2E_PROBE_MAX, "set_probes: between 1 and V2E_PROBE_MAX (64) pixels");
+    V2E_REQUIRE(pixel_index && out_dev, "set_probes: null pixel list or output buffer");
+    V2E_REQUIRE(h->n_clips == 1, "set_probes: handles of one clip only");
+    for (int j = 0; j < n; ++j) V2E_REQUIRE(pixel_index[j] >= 0 && pixel_index[j] < h->npx, "set_probes: pixel index outside [0, H * W)");
+    for (int j = 0; j < V2E_PROBE_MAX; ++j) h->probe_next.pix[j] = j < n ? pixel_index[j] : 0; // (all of it is part of a graph's key)
+    h->probe_next.n = n; h->probe_next_out = out_dev;
+    return 0;
+}
+
+// What a probed run needs beside the caller's buffer: the model-state planes (the caller's, else the library's own) and zeroed
+// counters for the row pass.  Blocking only when something has to be (re)allocated.
+static int probe_reserve(v2e_emu *h, int n_frames)
+{
+    if (!h->dbg_diff && !h->probe_planes) V2E_HIP(hipMalloc((void **)&h->probe_planes, sizeof(double) * 3 * (size_t)h->npx_pad));
+    const size_t need = (size_t)n_frames * h->probe_run.n * 2 + 1;
+    if (need > h->probe_cnt_cap) {
+        V2E_HIP(hipDeviceSynchronize()); // (a run before may still count into the old one)
+        h->drop_graphs();
+        if (h->probe_cnt) V2E_HIP(hipFree(h->probe_cnt));
+        h->probe_cnt = nullptr; h->probe_cnt_cap = 0;
+        V2E_HIP(hipMalloc((void **)&h->probe_cnt, sizeof(unsigned int) * need));
+        h->probe_cnt_cap = need;
+    }
     return 0;
 }
 
@@ -1646,6 +1685,11 @@ static int enqueue_run(v2e_emu *h, const v2e_emu_params *p, const KArgs &a, cons
     const size_t esz = dtype == V2E_DT_U8 ? 1 : (dtype == V2E_DT_F32 ? 4 : 8);
     V2E_HIP(zero_async(recs, sizeof(v2e_frame_rec) * (size_t)n_frames * h->n_clips, s));
     dim3 gridw(v2e_cdiv((int64_t)h->nwaves * WAVE, BLOCK), h->n_clips);
+    // v2e_emu_set_probes: the taps below carry no marks of their own (a profiled run times them with the kernel they follow)
+    const V2EProbeSet &ps = h->probe_run;
+    const size_t probe_stride = (size_t)ps.n * V2E_PROBE_FIELDS;
+    const size_t probe_words = (size_t)n_frames * ps.n * 2 + 1;
+    if (ps.n) V2E_HIP(zero_async(h->probe_cnt, sizeof(unsigned int) * probe_words, s));
     for (int f = 0; f < n_frames; ++f) {
         const void *fr = (const char *)frames + (size_t)f * h->n_clips * h->npx * esz;
         const FrameCtl *ctl = r.run_ctl + (size_t)f * h->n_clips;
@@ -1664,6 +1708,7 @@ static int enqueue_run(v2e_emu *h, const v2e_emu_params *p, const KArgs &a, cons
         }
         int rc = launch_count(h, a, p->f64_state, fr, dtype, ctl, r.run_fidx, (uint32_t)f, nullptr, nullptr, rec, s);
         if (rc) return rc;
+        if (ps.n && (rc = v2e_probe_tap_count(ps, fr, dtype, a.dbg_lognew, a.dbg_diff, h->probe_out + (size_t)f * probe_stride, s))) return rc;
         V2E_MARK(4 * f + 1);
         k_rank<<<gridw, BLOCK, 0, s>>>(a, ctl, rec, nullptr, 0);
         V2E_MARK(4 * f + 2);
@@ -1671,9 +1716,16 @@ static int enqueue_run(v2e_emu *h, const v2e_emu_params *p, const KArgs &a, cons
         V2E_MARK(4 * f + 3);
         if (p->f64_state) k_emit<double><<<gridw, BLOCK, 0, s>>>(a, ctl, rec, rec_prev, nullptr, r.run_fidx, (uint32_t)f, nullptr, 0, (float4 *)events, cap);
         else k_emit<float><<<gridw, BLOCK, 0, s>>>(a, ctl, rec, rec_prev, nullptr, r.run_fidx, (uint32_t)f, nullptr, 0, (float4 *)events, cap);
+        if (ps.n && (rc = v2e_probe_tap_emit(ps, a.lp, a.base, p->f64_state, a.pos_thres, a.neg_thres, a.scalar_thres, p->pos_thres_scalar,
+                                             p->neg_thres_scalar, h->probe_out + (size_t)f * probe_stride, s))) return rc;
     }
     V2E_MARK(4 * n_frames);
 #undef V2E_MARK
+    if (ps.n) { // the signal ON / OFF rows at the probed pixels, frame by frame: one pass over the run's rows
+        int rc = v2e_probe_count_rows(ps, events, cap, recs, n_frames, h->W, h->probe_cnt, h->probe_cnt + probe_words - 1, h->probe_out,
+                                      h->n_cu, s);
+        if (rc) return rc;
+    }
     V2E_HIP(hipGetLastError());
     return 0;
 }
@@ -2554,6 +2606,9 @@ static std::vector<unsigned char> graph_key(const v2e_emu *h, const v2e_emu_para
         push(h->csr_ap.data(), sizeof(double) * h->csr_ap.size()); push(h->csr_ah.data(), sizeof(double) * h->csr_ah.size());
         push(h->csr_steps.data(), sizeof(int) * h->csr_steps.size());
     }
+    if (h->probe_run.n) { // the probed pixels travel in the launches; their buffers are baked in
+        push(&h->probe_run, sizeof(h->probe_run)); push(&h->probe_out, sizeof(h->probe_out)); push(&h->probe_cnt, sizeof(h->probe_cnt));
+    }
     if (chain) {
         push(&h->ch_K, sizeof(h->ch_K)); push(&h->ch_E, sizeof(h->ch_E)); push(&h->ch_fused, sizeof(h->ch_fused)); push(&h->ch_nD, sizeof(h->ch_nD));
         push(&h->ch_max_blocks, sizeof(h->ch_max_blocks));
@@ -2599,8 +2654,13 @@ int v2e_emu_run(v2e_emu *h, const v2e_emu_params *p, const void *frames, int dty
                 const double *t_frame, uint32_t frame_idx0, float *events, uint64_t cap, v2e_frame_rec *recs_dev,
                 int flags, void *stream)
 {
+    if (h) { // v2e_emu_set_probes is one shot: this run takes the setting, whatever becomes of it
+        h->probe_run = h->probe_next; h->probe_out = h->probe_next_out;
+        h->probe_next.n = 0; h->probe_next_out = nullptr;
+    }
     int rc = check_params(h, p);
     if (rc) return rc;
+    const bool probed = h->probe_run.n > 0;
     V2E_REQUIRE(p->rng_mode == V2E_RNG_PHILOX, "v2e_emu_run is the device-resident Philox path");
     V2E_REQUIRE(frames && t_prev && t_frame && events && recs_dev && n_frames > 0, "bad run args");
     V2E_REQUIRE(dtype == V2E_DT_U8 || dtype == V2E_DT_F32 || dtype == V2E_DT_F64, "bad frame dtype");
@@ -2608,7 +2668,8 @@ int v2e_emu_run(v2e_emu *h, const v2e_emu_params *p, const void *frames, int dty
                 "a run with a CSDVS surround needs v2e_emu_set_csdvs_run for exactly these frames (one clip)");
     const bool chain_ok = chain_eligible(h, p, dtype);
     V2E_REQUIRE(!(flags & V2E_RUN_REQUIRE_CHAIN) || chain_ok, "k_chain cannot run this configuration (max_iters, photoreceptor noise or float64 log frames)");
-    const bool chain = chain_ok && ((flags & V2E_RUN_REQUIRE_CHAIN) || !(flags & V2E_RUN_PER_FRAME_KERNELS));
+    V2E_REQUIRE(!(flags & V2E_RUN_REQUIRE_CHAIN) || !probed, "k_chain records no single-pixel states: a run with probes set (v2e_emu_set_probes) goes through the per-frame kernels");
+    const bool chain = chain_ok && !probed && ((flags & V2E_RUN_REQUIRE_CHAIN) || !(flags & V2E_RUN_PER_FRAME_KERNELS));
     const int mode = flags & 3; // 0 plain launches, V2E_RUN_GRAPH, V2E_RUN_PROFILE
     const bool pipelined = (flags & V2E_RUN_PIPELINED) && mode == 0 && chain;
     V2E_HIP(hipSetDevice(h->device));
@@ -2625,7 +2686,12 @@ int v2e_emu_run(v2e_emu *h, const v2e_emu_params *p, const void *frames, int dty
     h->last_fpl = chain ? h->ch_K : 1;
     h->last_fpb = chain ? h->ch_E : 1;
     h->ch_last_launches = (chain && p->refractory_period_s > 0) ? (n_frames + h->ch_K - 1) / h->ch_K + 1 : 0; // (chain_plan's length)
-    const KArgs a = make_kargs(h, p);
+    KArgs a = make_kargs(h, p);
+    if (probed) {
+        rc = probe_reserve(h, n_frames);
+        if (rc) return rc;
+        if (!a.dbg_diff) { a.dbg_lognew = h->probe_planes; a.dbg_cms = a.dbg_lognew + h->npx_pad; a.dbg_diff = a.dbg_cms + h->npx_pad; }
+    }
     if (pipelined)
         return run_pipelined(h, p, a, frames, dtype, n_frames, t_prev, t_frame, frame_idx0, events, cap, recs_dev,
                              (flags & V2E_RUN_FRAMES_RESIDENT) != 0, s);

@@ -19,10 +19,12 @@ Random numbers come in two modes, selected with the extra key
            copy of the event list.  `generate_events_batch` keeps a whole clip on device.
 
 `show_dvs_model_state` / `save_dvs_model_state` (emulator.py:580-617, 756-764) and `record_single_pixel_states`
-(emulator.py:279-300, 985-1009) are host pass-throughs: the named state planes are read back from the device after every frame
-(three of them -- log_new_frame, c_minus_s_frame, diff_frame -- are left in extra planes by k_count while one of the two options
-is on, v2e_emu_set_model_state_planes) and displayed / saved through cv2 where it is importable, resp. recorded and pickled
-as the reference does; both put generate_events on the step-wise kernels.  `hdr=True`
+(emulator.py:279-300, 985-1009) are host pass-throughs in generate_events: the named state planes are read back from the device after
+every frame (three of them -- log_new_frame, c_minus_s_frame, diff_frame -- are left in extra planes by k_count while one of the two
+options is on, v2e_emu_set_model_state_planes) and displayed / saved through cv2 where it is importable, resp. recorded and pickled
+as the reference does; both put generate_events on the step-wise kernels.  In generate_events_batch the recorder's pixel -- and up to
+64 pixels of the caller's, `probe_pixels` -- is read on the device instead (v2e_emu_set_probes, csrc/probe.hip: nine float64 per
+pixel and frame come back with the run's result; such a run takes the per-frame kernels, not k_chain).  `hdr=True`
 (log-encoded input, emulator.py:304, 666), `photoreceptor_noise=True` (emulator.py:694-703), `scidvs=True` (float64 and float32
 state: torch's float32 sinh is restated bit for bit in include/v2e_detmath.h)
 and the centre-surround pixel (`cs_lambda_pixels`, emulator.py:1061-1124: the diffuser is stepped on the device between
@@ -139,6 +141,51 @@ def _cleanup_at_exit(ref):
         emu.cleanup()
 
 
+PIXEL_STATE_SERIES = ("time",) + _capi.PROBE_FIELD_NAMES  # the reference's ten series, in its order (emulator.py:287-294)
+
+
+def probe_pixel_indices(pixels, H, W, most=_capi.PROBE_MAX):
+    """[(a, b), ...] -- addressed as the reference's plane[a, b], row then column, like record_single_pixel_states -- as the
+    indices a * W + b v2e_emu_set_probes takes.  ValueError for more than `most` pixels, for anything that is not a pair of
+    integers and for a pixel outside the H x W array (no negative indices: an event row never carries one)."""
+    pixels = list(pixels)
+    if len(pixels) > most:
+        raise ValueError("at most %d pixels can be probed in one run, got %d" % (most, len(pixels)))
+    out = []
+    for px in pixels:
+        try:
+            a, b = px
+            a, b = int(a.__index__()), int(b.__index__())
+        except (TypeError, ValueError, AttributeError):
+            raise ValueError("a probed pixel is a pair of integers (row, column), got %r" % (px,))
+        if not (0 <= a < H and 0 <= b < W):
+            raise ValueError("probed pixel %r lies outside the %d x %d pixel array" % (px, H, W))
+        out.append(a * W + b)
+    return out
+
+
+def append_pixel_states(states, count, max_samples, times, block, pos_thres=None, neg_thres=None):
+    """What emulator.py:985-1009 does frame after frame, for the frames of one device-resident run: `block` [F, PROBE_FIELDS]
+    (one probe of v2e_emu_set_probes, the clip's very first frame not among them) and their frame times go to samples count,
+    count + 1, ... of the ten series while there is room; pos_thres / neg_thres: the Python-float thresholds, recorded instead of
+    the block's where the reference holds scalars (emulator.py:992-995).  Returns (new count, stop): stop when a frame came after
+    the series were full -- where the reference saves the file and ends the recording."""
+    F = len(times)
+    n = max(0, min(F, max_samples - count))
+    for k in range(count, count + n):
+        if k % 250 == 0:
+            logger.info(f'recorded {k} single pixel states')
+    sl = slice(count, count + n)
+    states['time'][sl] = np.asarray(times, dtype=np.float64)[:n]
+    for i, name in enumerate(_capi.PROBE_FIELD_NAMES):
+        states[name][sl] = block[:n, i]
+    if pos_thres is not None:
+        states['pos_thres'][sl] = pos_thres
+    if neg_thres is not None:
+        states['neg_thres'][sl] = neg_thres
+    return count + n, F > n
+
+
 def default_event_capacity(n_frames, H, W):
     """Event rows a device-resident run of n_frames frames of H x W gets when no cap is given: 4 events per pixel and frame (the
     reference never drops events; a run that exceeds this raises and leaves the instance unusable until reset()), bounded to
@@ -155,7 +202,10 @@ class _PendingRun:
         self.counts, self.start, self.return_device, self.empty, self.dts = counts, start, return_device, empty, dts
         self.ticket = ticket  # pipelined runs (v2e_emu_run, RUN_PIPELINED): what result() waits for on the host (v2e_emu_run_wait)
         self._res = None
+        self.probe_rec, self.probe_claim = False, 0  # the recorder's pixel is probe 0 of the run; the samples it will add
         self.which = None     # the buffer set the run's rows and records are in
+        self.probes = None    # probe_pixels=...: the ten series of the probed pixels, float64 [F_run, P] each (after result())
+        self.probe_dev = None  # a probed run's device block [F_run][probes][PROBE_FIELDS], until result() reads it
         self.frame0 = 0       # 0-based index of the run's first frame in the clip (the HDF5 frame_idx slot)
 
     @property
@@ -404,10 +454,10 @@ class EventEmulator(object):
                 pass
         if getattr(self, "video_writers", None):
             self.video_writers = {}
+        self._write_held_runs()  # every run enqueued while the sinks were open (or the recorder on) reaches them before they close
         if getattr(self, "record_single_pixel_states", None) is not None:  # emulator.py:428-429
             self.save_recorded_single_pixel_states()
             self.record_single_pixel_states = None
-        self._write_held_runs()  # every run enqueued while the sinks were open reaches them before they close
         for w in ("dvs_h5", "dvs_aedat2", "dvs_aedat4", "dvs_text"):
             o = getattr(self, w, None)
             if o is not None:
@@ -985,13 +1035,14 @@ class EventEmulator(object):
         self.cs_steps_taken.append(steps)
 
     # ------------------------------------------------------------- device-resident clip
-    def generate_events_batch(self, frames, t_frames, return_device=False, use_graph=True, cap=None):
+    def generate_events_batch(self, frames, t_frames, return_device=False, use_graph=True, cap=None, *, probe_pixels=None):
         """Philox mode: run a whole clip [F,H,W] with timestamps t_frames[F] on device.
 
         Equivalent to calling generate_events once per frame (same events, same order) but
         with no host synchronisation between frames.  Returns (events, counts): events is
         an [N,4] float32 array (or device tensor) of all frames' events concatenated,
         counts[f] the number of events of frame f (0 for the very first frame).
+        probe_pixels: see generate_events_batch_async; the series are left in `last_probes`.
         """
         pipelined = None
         if use_graph is True:
@@ -1002,11 +1053,15 @@ class EventEmulator(object):
             if seen.get(n, 0) == 0:
                 use_graph, pipelined = 0, False
             seen[n] = seen.get(n, 0) + 1
-        return self.generate_events_batch_async(frames, t_frames, return_device=return_device, use_graph=use_graph,
-                                                cap=cap, _single_buffer=True, pipelined=pipelined).result()
+        pend = self.generate_events_batch_async(frames, t_frames, return_device=return_device, use_graph=use_graph,
+                                                cap=cap, _single_buffer=True, pipelined=pipelined, probe_pixels=probe_pixels)
+        res = pend.result()
+        if probe_pixels is not None:
+            self.last_probes = pend.probes
+        return res
 
     def generate_events_batch_async(self, frames, t_frames, return_device=False, use_graph=True, cap=None,
-                                    _single_buffer=False, pipelined=None, frames_resident=False):
+                                    _single_buffer=False, pipelined=None, frames_resident=False, *, probe_pixels=None):
         """generate_events_batch without waiting for the device: enqueues the run and returns a handle whose
         result() gives (events, counts).  The host can prepare and enqueue the next run (it executes behind this one
         on the same stream) before reading this one's result: two sets of event / record buffers alternate, so a
@@ -1019,14 +1074,21 @@ class EventEmulator(object):
         (v2e_emu_run, RUN_PIPELINED): the throughput mode of a loop that keeps one run enqueued ahead (bench.py).  The current stream then
         orders the pixel state only; result() waits for the rows.  frames_resident=True: the caller vouches that nothing enqueued on
         the current stream still writes `frames`; the run's head then need not wait for the chain of the run before.
+        probe_pixels=[(a, b), ...] (at most 64; one fewer beside record_single_pixel_states): the handle carries `.probes` after
+        result(), a dict of the reference's ten single-pixel series (emulator.py:985-1009; PIXEL_STATE_SERIES) as float64 arrays
+        [frames of the run, P], `time` broadcast, the pixels addressed as the reference's plane[a, b].  An emulator built with
+        record_single_pixel_states records that pixel run after run the same way (appended to single_pixel_states in the order the
+        runs were enqueued, when their results are read -- by the caller, by the call that reuses a dropped handle's buffers, or by
+        cleanup()).  Either makes the run a probed one: the per-frame kernels instead of k_chain, never pipelined, three small
+        launches beside them (v2e_emu_set_probes).
         """
         if getattr(self, "_failed", None):
             raise _capi.V2EAmdError("a previous device-resident run failed (%s); call reset()" % self._failed)
         if self.rng_mode != "philox":
             raise ValueError("generate_events_batch needs rng_mode='philox' (tape mode needs the host per frame)")
-        if self._wants_states():
-            raise ValueError("show_dvs_model_state / record_single_pixel_states read the state after every frame: use "
-                             "generate_events per frame")
+        if self.show_dvs_model_state is not None:
+            raise ValueError("show_dvs_model_state / save_dvs_model_state show or save a picture of the state after every frame: "
+                             "use generate_events per frame")
         if isinstance(frames, np.ndarray):
             if frames.dtype not in (np.uint8, np.float32, np.float64):
                 frames = frames.astype(np.float64)
@@ -1035,6 +1097,11 @@ class EventEmulator(object):
         t_frames = [float(t) for t in t_frames]
         if len(t_frames) != F:
             raise ValueError("need one timestamp per frame")
+        user_idx = probe_pixel_indices(probe_pixels, H, W) if probe_pixels is not None else []
+        if self.record_single_pixel_states is not None:
+            probe_pixel_indices([self.record_single_pixel_states], H, W)
+            if len(user_idx) >= _capi.PROBE_MAX:
+                raise ValueError("at most %d pixels can be probed beside record_single_pixel_states" % (_capi.PROBE_MAX - 1))
         eng = self._ensure_engine(H, W)
         frames_dev = eng.to_device_frame(frames)
         counts = np.zeros(F, dtype=np.int64)
@@ -1051,7 +1118,10 @@ class EventEmulator(object):
         nrun = F - start
         if nrun <= 0:
             empty = torch.empty((0, 4), dtype=torch.float32, device=eng.device)
-            return _PendingRun(self, None, None, None, counts, start, return_device, empty)
+            pend = _PendingRun(self, None, None, None, counts, start, return_device, empty)
+            if probe_pixels is not None:
+                pend.probes = {k: np.empty((0, len(user_idx))) for k in PIXEL_STATE_SERIES}
+            return pend
         t_prev = []
         tp = float(self.t_previous)
         for f in range(start, F):
@@ -1102,6 +1172,21 @@ class EventEmulator(object):
             _capi.check(eng.lib.v2e_emu_set_csdvs_run(eng._h, scratch.data_ptr(), lp_new.data_ptr(), ap, ah, ns, nrun,
                                                       float(self.MAX_CHANGE_TO_TERMINATE_EULER_SURROUND_STEPPING),
                                                       cs_steps_dev.data_ptr()), "v2e_emu_set_csdvs_run")
+        rec_claim = 0
+        if self.record_single_pixel_states is not None:
+            # emulator.py:985-1009 frame by frame: a frame that finds the series full saves the file and ends the recording.  Samples
+            # of runs enqueued and not yet read count as taken
+            held = self.__dict__.get("_sink_runs") or ()
+            room = self.SINGLE_PIXEL_MAX_SAMPLES - self.single_pixel_sample_count - sum(p.probe_claim for p in held)
+            if room <= 0:
+                self._write_held_runs()
+                if self.record_single_pixel_states is not None:
+                    self.save_recorded_single_pixel_states()
+                    self.record_single_pixel_states = None
+            else:
+                rec_claim = min(nrun, room)
+        probe_idx = (probe_pixel_indices([self.record_single_pixel_states], H, W) if self.record_single_pixel_states is not None
+                     else []) + user_idx
         P = self._params()
         if cap is None:
             cap = default_event_capacity(nrun, H, W)
@@ -1132,6 +1217,10 @@ class EventEmulator(object):
             ug |= _capi.RUN_ONE_FRAME_PER_LAUNCH  # the speculating chain would redo most of its launches
         if (ug & (_capi.RUN_GRAPH | _capi.RUN_PROFILE)) == 0 and (pipelined or pipelined is None) and not _single_buffer:
             ug |= _capi.RUN_PIPELINED | (_capi.RUN_FRAMES_RESIDENT if frames_resident else 0)
+        probe_dev = None
+        if probe_idx:
+            probe_dev = eng.probe_buffer(nrun, len(probe_idx), which)
+            eng.set_probes(probe_idx, probe_dev)
         eng.run(P, frames_dev[start:], t_prev, t_frames[start:], self.frame_counter, ev, recs, use_graph=ug)
         ticket = None
         if ug & _capi.RUN_PIPELINED:
@@ -1148,10 +1237,14 @@ class EventEmulator(object):
         pend = _PendingRun(self, ev, recs, done, counts, start, return_device, None, dts, ticket)
         pend.cs_steps_dev = cs_steps_dev
         pend.which, pend.frame0 = which, self.frame_counter - nrun
+        pend.probe_dev, pend.probe_rec, pend.probe_claim = probe_dev, self.record_single_pixel_states is not None, rec_claim
+        pend.times = t_frames[start:]
+        # (the thresholds the reference would record where it holds Python floats, emulator.py:992-995: as they are now)
+        pend.thres = (self.pos_thres if type(self.pos_thres) is float else None, self.neg_thres if type(self.neg_thres) is float else None)
         slots[which] = weakref.ref(pend)
-        if self._sinks_open():
-            # held strongly until its rows are in the files, in the order the runs were enqueued (a handle the caller drops is
-            # written by the call that reuses its buffer set, or by cleanup())
+        if self._sinks_open() or pend.probe_rec:
+            # held strongly until its rows are in the files (its samples in single_pixel_states), in the order the runs were enqueued
+            # (a handle the caller drops is written by the call that reuses its buffer set, or by cleanup())
             self.__dict__.setdefault("_sink_runs", []).append(pend)
         return pend
 
@@ -1194,6 +1287,8 @@ class EventEmulator(object):
         self.num_events_total += total
         self.num_events_on += int(r["n_on"].sum())
         self.num_events_off += int(r["n_off"].sum())
+        if pend.probe_dev is not None:
+            self._collect_probes(pend)
         out = pend.ev[0, :total]
         host = None if pend.return_device or total == 0 else out.cpu().numpy()
         if held and held[0] is pend:
@@ -1202,3 +1297,30 @@ class EventEmulator(object):
         if pend.return_device:
             return out, pend.counts
         return host, pend.counts
+
+    def _collect_probes(self, pend):
+        """The block a probed run left on the device (v2e_emu_set_probes): the recorder's pixel, if it was on, is probe 0 and goes to
+        single_pixel_states as the per-frame path would have put it there (append_pixel_states); the caller's pixels to pend.probes."""
+        blk = self._engine.read_after(pend.probe_dev, pend.done)  # [F_run][probes][PROBE_FIELDS]
+        pend.probe_dev = None
+        times = np.asarray(pend.times, dtype=np.float64)
+        pos, neg = pend.thres
+        first = 0
+        if pend.probe_rec:
+            first = 1
+            if self.record_single_pixel_states is not None:
+                self.single_pixel_sample_count, stop = append_pixel_states(
+                    self.single_pixel_states, self.single_pixel_sample_count, self.SINGLE_PIXEL_MAX_SAMPLES, times, blk[:, 0, :], pos, neg)
+                if stop:  # emulator.py:1007-1009
+                    self.save_recorded_single_pixel_states()
+                    self.record_single_pixel_states = None
+        if blk.shape[1] > first:
+            user = blk[:, first:, :]
+            d = {"time": np.repeat(times[:, None], user.shape[1], axis=1)}
+            for i, name in enumerate(_capi.PROBE_FIELD_NAMES):
+                d[name] = np.ascontiguousarray(user[:, :, i])
+            if pos is not None:
+                d["pos_thres"][:] = pos
+            if neg is not None:
+                d["neg_thres"][:] = neg
+            pend.probes = d

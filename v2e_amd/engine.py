@@ -229,6 +229,34 @@ class EmuEngine:
         a, b, c = planes if planes is not None else (None, None, None)
         check(self.lib.v2e_emu_set_model_state_planes(self._h, _ptr(a), _ptr(b), _ptr(c)), "v2e_emu_set_model_state_planes")
 
+    def set_probes(self, pixel_index, out_dev):
+        """The next run() records the single-pixel model states of the pixels `pixel_index` (row * W + col each) into out_dev, a
+        float64 device tensor [F][len(pixel_index)][PROBE_FIELDS] (v2e_emu_set_probes; one shot); None / empty cancels."""
+        n = 0 if pixel_index is None else len(pixel_index)
+        arr = (C.c_int32 * max(n, 1))(*[int(v) for v in (pixel_index or ())])
+        check(self.lib.v2e_emu_set_probes(self._h, arr, n, _ptr(out_dev) if n else None), "v2e_emu_set_probes")
+
+    def probe_buffer(self, n_frames, n_probes, which=0):
+        """Device float64 [F][P][PROBE_FIELDS] for set_probes, cached per (F, P, set) like alloc_recs: the hipGraph of a probed run
+        bakes the pointer in."""
+        cache = self.__dict__.setdefault("_probe_cache", {})
+        key = (n_frames, n_probes, which)
+        if key not in cache:
+            if len(cache) > 8:
+                cache.clear()
+            cache[key] = torch.empty((n_frames, n_probes, _capi.PROBE_FIELDS), dtype=torch.float64, device=self.device)
+        return cache[key]
+
+    def read_after(self, t, done_event):
+        """A small device tensor as a numpy array, copied on the side stream of read_recs_after once `done_event` has completed."""
+        cs = self.__dict__.get("_copy_stream")
+        if cs is None:
+            cs = self._copy_stream = torch.cuda.Stream(self.device)
+        with torch.cuda.stream(cs):
+            if done_event is not None:
+                cs.wait_event(done_event)
+            return t.cpu().numpy()
+
     def shot(self, P, frame_dev, frame_idx, shot_rand):
         check(self.lib.v2e_emu_shot(self._h, C.byref(P), _ptr(frame_dev), _DT[frame_dev.dtype],
                                     int(frame_idx), _ptr(shot_rand), self.stream), "v2e_emu_shot")

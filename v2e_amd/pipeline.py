@@ -457,7 +457,11 @@ class VideoToEvents:
         flush) that completed frames, device tensors as `render_run` returns them (uint8 frames with dvs_u8), with the render
         stream current; without it the frames are gathered on the device and left in `dvs_frames` / `dvs_frame_times` as
         `run` leaves them.  The renderer's read-backs (one per chunk in DURATION and AREA_COUNT mode) are added to
-        `host_syncs`.  Events, counts and event files are what they are without a renderer."""
+        `host_syncs`.  Events, counts and event files are what they are without a renderer.
+
+        An emulator built with record_single_pixel_states records its pixel across the chunks as it does across `run`'s one run (the
+        sample index runs on over the chunk boundaries; `emu.cleanup()` writes the file): every chunk is then a probed run, on the
+        per-frame kernels and not pipelined (EventEmulator.generate_events_batch_async)."""
         N, H, W = stream_source_shape(frames_u8)
         P, bs = N - 1, self.batch_size
         chunks = stream_chunks(P, bs, chunk_pairs)
