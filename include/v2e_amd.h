@@ -585,6 +585,32 @@ int v2e_render_run(const float *events, int64_t n_rows, const int64_t *pkt_off, 
                    int want_frames, int32_t *diff, double *frames_out, uint8_t *frames_u8_out, double *cur_out, int bins_y,
                    int bins_x, double y_lo, double y_hi, double x_lo, double x_hi, double full_scale, void *stream);
 
+/* The reference's synthetic input sources (v2e.py:580-612, --synthetic_input=scripts.<name>) rendered on the device
+ * (v2e_amd/csrc/synth.hip; host side v2e_amd/synthetic.py).  Every entry writes a block of n consecutive frames into the
+ * caller's device buffer out[n][H][W] in one launch and nothing outside it; all arithmetic is float64 in the reference's
+ * order of operations.
+ * v2e_synth_dots: scripts/moving_dot.py:26-54, 156-183 and scripts/particles.py:187-197, 213-241 (fill_dot over a background
+ * frame).  Frame f draws the dots offs[f] .. offs[f + 1] (device int32 [n + 1], from 0) in list order: centres (device
+ * float64 [dots][2]: x, y) and boxes (device int32 [dots][2]: x0, y0, the rounded centre as the host's Python round() gave
+ * it).  A pixel in [x0 - d, x0 + d) x [y0 - d, y0 + d) becomes bg + (fg - bg) * v, v = peak * exp(-dist2 / (sigma * sigma))
+ * with dist2 from the float centre, v > 1 -> 1, else v < low_cut -> 0 (moving_dot.py:44-49: peak 10, low_cut .01;
+ * particles.py:236-240: peak 2, no low cut: pass a negative one); clip != 0 clamps the result to 0..255 (moving_dot.py:50-53).
+ * Where boxes overlap the dot later in the list wins, as in the reference's sequential loop; a pixel no box covers is bg; a
+ * box is clipped at the frame edge (particles.py:232).  out_dtype: V2E_DT_U8 (the C conversion numpy applies when a double is
+ * stored into a uint8 array), V2E_DT_F32 (particles' float32 frame) or V2E_DT_F64. */
+int v2e_synth_dots(const double *centres, const int32_t *boxes, const int32_t *offs, int n, int H, int W, void *out, int out_dtype,
+                   double bg, double fg, double sigma, int d, double peak, double low_cut, int clip, void *stream);
+/* v2e_synth_gradients: gradients.im_function (scripts/gradients.py:117-140) as uint8.  p: device float64 [n], the bump centre
+ * of every frame (gradients.py:125; p2 = p + w2 * 2 follows from it); low, high, slope = -diff / w2 and w2 are the call's
+ * constants as the host computes them (gradients.py:121-124).  The three masked assignments are applied in the reference's order. */
+int v2e_synth_gradients(const double *p, int n, int H, int W, uint8_t *out, double low, double high, double slope, double w2,
+                        void *stream);
+/* v2e_synth_barberpole: barberpole.bb_func (scripts/barberpole.py:155-163) inside the pole mask, bg outside
+ * (barberpole.py:85-98, 139-140).  t: device float64 [n], the frame times.  Pole pixels (minx < x < maxx and miny < y < maxy,
+ * strict) are uint8(floor(low + diff * 0.5 * (1 + tanh(10 * sin(two_pi * (y - tan_a * x - t * speed) / wavelength))))). */
+int v2e_synth_barberpole(const double *t, int n, int H, int W, uint8_t *out, double low, double diff, double tan_a, double speed,
+                         double two_pi, double wavelength, int minx, int maxx, int miny, int maxy, int bg, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,9 @@ SIGNATURES = {
     "v2e_slomo_prep_tab": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "v2e_slomo_fuse_tab": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "v2e_f32_to_u8_trunc_tab": (_i, [_vp, _vp, _vp, _i, _i, C.c_float, _vp]),
+    "v2e_synth_dots": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _d, _d, _d, _i, _d, _d, _i, _vp]),
+    "v2e_synth_gradients": (_i, [_vp, _i, _i, _i, _vp, _d, _d, _d, _d, _vp]),
+    "v2e_synth_barberpole": (_i, [_vp, _i, _i, _i, _vp, _d, _d, _d, _d, _d, _d, _i, _i, _i, _i, _i, _vp]),
 }
 
 # dev entry points the library exports outside include/v2e_amd.h: typed by lib() when present, never required
