@@ -13,7 +13,9 @@ TAPE_FIXTURES = ["tape_defaults_40x48", "tape_noisy_40x48", "tape_clean_40x48", 
                  "tape_pnoise_40x48"]  # photoreceptor noise: tests/golden/make_golden_pnoise.py
 PHILOX_FIXTURES = ["philox_moving_dot_64x64", "philox_defaults_346x260", "philox_noisy_346x260",
                    "philox_refractory_346x260", "philox_noisy_1280x720", "philox_hdr_97x131",
-                   "philox_pnoise_97x131"]
+                   "philox_pnoise_97x131",
+                   # float frames at the edges of the float record path, float64 / float32 state: tests/golden/make_golden_float_frames.py
+                   "philox_f64frames_33x37", "philox_f32frames_f32state_33x37"]
 # 1280x720 runs long enough for full 32-frame chain launches, a validating successor and a wrap of the ring of frame
 # slots (104 frames, noisy preset), and with a refractory period of 2 ms (26 frames): tests/golden/make_golden_hd_long.py
 PHILOX_HD_FIXTURES = ["philox_noisy_1280x720_long", "philox_refractory_1280x720"]
