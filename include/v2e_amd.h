@@ -611,6 +611,35 @@ int v2e_synth_gradients(const double *p, int n, int H, int W, uint8_t *out, doub
 int v2e_synth_barberpole(const double *t, int n, int H, int W, uint8_t *out, double low, double diff, double tan_a, double speed,
                          double two_pi, double wavelength, int minx, int maxx, int miny, int maxy, int bg, void *stream);
 
+/* Dense event tensors from the rows of a device-resident run (v2e_amd/csrc/tensorize.hip; host side v2e_amd/tensors.py,
+ * EventTensorizer).  Rows are events[n][4] = (t, x = column, y = row, p = +-1), in any order.  Window k of the clip is [B_k, B_k+1) in
+ * float64 with the float32 t widened: B_k = t_start + (double)k * window_s (bounds null), or the ascending device table
+ * bounds[] (then bounds[0] is the start of the launch's first window and nk + 1 entries are read).  A launch covers the nk
+ * windows from clip index k0 on; with has_open the last of them is the clip's open window, whose planes are the carried *_open
+ * buffers; the planes of the complete windows lie in count / voxel_acc / surf_keys.  Every update is a no-return integer atomic, so
+ * the result does not depend on the order of the rows.
+ * v2e_tensorize_scatter: one pass over the rows; each representation is enabled by its *_open pointer.  count: int32 [.,2,H,W]
+ * (channel 0 OFF, 1 ON), += 1.  voxel: int64 [.,voxel_bins,H,W] in units of 2^-24: tau = (bins - 1) * ((t - B_k) / (B_k+1 - B_k)),
+ * b0 = floor(tau), q1 = llrint((tau - b0) * 2^24), q0 = 2^24 - q1; p * q0 is added to bin b0 and, when q1 != 0, p * q1 to bin
+ * b0 + 1; voxel_acc holds only the complete windows v_a .. v_b - 1 (launch-local), the others are skipped.  surface: uint32
+ * [.,2,H,W], the maximum of an order-preserving key of t (0 = none).  A row with x outside [0,W), y outside [0,H), a fractional
+ * coordinate, p other than +-1 or a NaN t is written nowhere and counted in counters[0] (n_bad); a row before the launch's first
+ * window in counters[1] (n_before), at or after its last bound in counters[2] (n_after); counters (device uint64 [3]) may be null.
+ * events must be 16-byte aligned. */
+int v2e_tensorize_scatter(const float *events, int64_t n, int H, int W, double t_start, double window_s, const double *bounds,
+                          int64_t k0, int nk, int has_open, int32_t *count, int32_t *count_open, int64_t *voxel_acc,
+                          int64_t *voxel_open, int v_a, int v_b, int voxel_bins, uint32_t *surf_keys, uint32_t *surf_open,
+                          uint64_t *counters, void *stream);
+/* v2e_tensorize_move_zero: 32-bit words; dst[0 .. n_words) = carry[0 .. n_carry_words) followed by zeros, then carry = 0 (the
+ * plane of the window that was open becomes the first plane of the output).  16-byte stores where dst, carry and the counts allow. */
+int v2e_tensorize_move_zero(void *dst, int64_t n_words, void *carry, int64_t n_carry_words, void *stream);
+/* v2e_tensorize_voxel_finish: out[i] = (float)((double)acc[i] * 2^-24), i < n; clear != 0 zeroes acc behind the read. */
+int v2e_tensorize_voxel_finish(int64_t *acc, int64_t n, float *out, int clear, void *stream);
+/* v2e_tensorize_surface_finish: in place on planes [n_planes][plane_words] of keys: the running maximum over the planes, starting
+ * from state[plane_words] (keys; a pixel without an event holds the key of -inf), decoded to the float32 time stamp; state = the
+ * maximum after the last plane. */
+int v2e_tensorize_surface_finish(void *planes, int n_planes, int64_t plane_words, uint32_t *state, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,10 @@ SIGNATURES = {
     "v2e_synth_dots": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _d, _d, _d, _i, _d, _d, _i, _vp]),
     "v2e_synth_gradients": (_i, [_vp, _i, _i, _i, _vp, _d, _d, _d, _d, _vp]),
     "v2e_synth_barberpole": (_i, [_vp, _i, _i, _i, _vp, _d, _d, _d, _d, _d, _d, _i, _i, _i, _i, _i, _vp]),
+    "v2e_tensorize_scatter": (_i, [_vp, _i64, _i, _i, _d, _d, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "v2e_tensorize_move_zero": (_i, [_vp, _i64, _vp, _i64, _vp]),
+    "v2e_tensorize_voxel_finish": (_i, [_vp, _i64, _vp, _i, _vp]),
+    "v2e_tensorize_surface_finish": (_i, [_vp, _i, _i64, _vp, _vp]),
 }
 
 # dev entry points the library exports outside include/v2e_amd.h: typed by lib() when present, never required
