@@ -6,7 +6,7 @@ frame_record_table's float branch; quotients of frame_body's floor division that
 directions, and quotients that are exact integers).
 
 Every test asserts which kernel ran: the pipeline and its frames per launch from last_pipeline(), the state type from the dtype
-of lp_log_frame, the frame type from the dtype of the array it passed in (chain_fn() in emu.hip picks the instantiation by
+of lp_log_frame, the frame type from the dtype of the array it passed in (chain_fn() in emu_chain_host.h picks the instantiation by
 exactly these)."""
 import numpy as np
 import pytest

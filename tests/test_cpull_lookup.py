@@ -73,7 +73,7 @@ def shim(tmp_path_factory):
     return lib
 
 
-def p2_of(nwaves):  # emu.hip launch_emission, single level
+def p2_of(nwaves):  # emu_chain_host.h launch_emission, single level
     p2 = 64
     while p2 < nwaves:
         p2 *= 2

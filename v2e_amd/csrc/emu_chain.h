@@ -1,4 +1,4 @@
-// emu_chain.h -- the device-resident run: K frames per chain launch, per-pixel state in registers (included by emu.hip).
+// emu_chain.h -- the device-resident run: K frames per chain launch, per-pixel state in registers (included by emu.hip; its host side: emu_chain_host.h).
 //
 // The frame-to-frame dependency of the DVS pixel model is per pixel, except for ONE global number per frame: the
 // frame's max event count M, and only through the refractory rule (emulator.py:830: the rule is applied iff

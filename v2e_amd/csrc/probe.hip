@@ -1,7 +1,7 @@
 // probe.hip -- single-pixel model states of a device-resident run (v2e_emu_set_probes) for gfx950 / MI355X.
 //
 // The reference's research recorder (--record_single_pixel_states, v2ecore/emulator.py:279-300, 985-1009) reads ten numbers
-// for one pixel after every frame.  A run that goes through the per-frame kernels (emu.hip: k_count -> k_rank -> k_scan ->
+// for one pixel after every frame.  A run that goes through the per-frame kernels (emu_kernels.h: k_count -> k_rank -> k_scan ->
 // k_emit) gets them from three small kernels enqueued with it, for up to V2E_PROBE_MAX pixels at once:
 //   k_probe_tap_count   behind k_count of frame f: new_frame, log_new_frame, diff_frame            emulator.py:666, 749-754
 //   k_probe_tap_emit    behind k_emit of frame f:  base_log_frame, lp_log_frame, the thresholds   emulator.py:936-942, 985
