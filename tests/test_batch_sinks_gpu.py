@@ -184,3 +184,65 @@ def test_hdf5_rows_and_frame_index_of_batch_runs(tmp_path):
             out[name] = {k: f[k][()] for k in ("events", "frame_idx", "frame", "frame_ts")}
     for k in out["pf"]:
         assert np.array_equal(out["pf"][k], out["bt"][k]), k
+
+
+def small_clip(n, H, W, seed):
+    rng = np.random.Generator(np.random.PCG64(seed))
+    return rng.integers(0, 256, size=(n, H, W)).astype(np.uint8), [i / 300 for i in range(n)]
+
+
+def text_emulator(tmp, name, **kw):
+    from v2e_amd import EventEmulator
+    kw = dict({k: v for k, v in KW.items() if not k.startswith("output_")}, **kw)
+    return EventEmulator(device="cuda", seed=7, rng_mode="philox", output_folder=str(tmp), dvs_text=name, **kw)
+
+
+@pytest.mark.gpu
+def test_cleanup_drops_the_held_runs_of_a_failed_instance(tmp_path, caplog):
+    """Three runs left to cleanup() with a text file open, the second one with too small an event buffer: the first run's rows
+    reach the file (what the per-frame path writes for its frames), the failed run and the one after it are dropped with one
+    error line, the file is closed, and the instance refuses frames until reset()."""
+    from v2e_amd import V2EAmdError
+    frames, times = small_clip(8, 37, 91, seed=3)
+    twin = text_emulator(tmp_path, "twin")
+    for f, t in zip(frames[:4], times[:4]):
+        twin.generate_events(f, t)
+    twin.cleanup()
+    emu = text_emulator(tmp_path, "fail")
+    emu.generate_events_batch_async(frames[:4], times[:4], use_graph=0, pipelined=False)
+    emu.generate_events_batch_async(frames[4:6], times[4:6], use_graph=0, pipelined=False, cap=1024)  # a fresh buffer set: 1 024 rows
+    emu.generate_events_batch_async(frames[6:], times[6:], use_graph=0, pipelined=False)  # (reuses the first run's set: written)
+    assert len(emu.__dict__["_sink_runs"]) == 2
+    text = emu.dvs_text
+    emu.cleanup()
+    errors = [r.getMessage() for r in caplog.records if r.levelname == "ERROR"]
+    assert len(errors) == 1 and "2 enqueued run(s) not written to the event files" in errors[0] and "capacity" in errors[0]
+    assert emu.dvs_text is None and not emu.__dict__["_sink_runs"] and text.file is None
+    want = body(str(tmp_path / "twin.txt"), True)
+    assert want.count(b"\n") > 1024 and body(str(tmp_path / "fail.txt"), True) == want
+    with pytest.raises(V2EAmdError, match="reset"):
+        emu.generate_events(frames[-1], times[-1] + 0.01)
+
+
+@pytest.mark.gpu
+def test_cleanup_twice_does_the_work_once(tmp_path, caplog):
+    """A centre-surround run left to cleanup(): the first call writes it, reports the CSDVS step statistics and closes the file
+    (the per-frame path's file); the second call logs nothing and touches no file."""
+    import logging
+    from v2e_amd.synth import int_gradient_frames
+    frames, times = int_gradient_frames(7, 8, 70, seed=71, noise=8, as_array=True), [i / 250 for i in range(7)]
+    cs = dict(cutoff_hz=300, cs_lambda_pixels=2.5, cs_tau_p_ms=3.0)
+    twin = text_emulator(tmp_path, "twin", **cs)
+    for f, t in zip(frames, times):
+        twin.generate_events(f, t)
+    twin.cleanup()
+    emu = text_emulator(tmp_path, "cs", **cs)
+    emu.generate_events_batch_async(frames, times, use_graph=0, pipelined=False)
+    path = str(tmp_path / "cs.txt")
+    with caplog.at_level(logging.INFO, logger="v2e_amd.emulator"):
+        emu.cleanup()
+        first, stamp, logged = open(path, "rb").read(), os.stat(path).st_mtime_ns, len(caplog.records)
+        emu.cleanup()
+    assert len(caplog.records) == logged and os.stat(path).st_mtime_ns == stamp and open(path, "rb").read() == first
+    assert sum("CSDVS steps statistics" in r.getMessage() for r in caplog.records) == 1
+    assert body(path, True) == body(str(tmp_path / "twin.txt"), True) and body(path, True).count(b"\n") > 0

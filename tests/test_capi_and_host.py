@@ -65,7 +65,8 @@ def test_emulator_constructor_surface():
     assert (e.sigma_thres, e.cutoff_hz, e.leak_rate_hz, e.shot_noise_rate_hz) == (0.02, 0, 0, 0)
 
 
-def test_emulator_errors_like_reference():
+def test_emulator_errors_like_reference(tmp_path, monkeypatch):
+    monkeypatch.chdir(tmp_path)
     from v2e_amd import EventEmulator
     e = EventEmulator()
     e.t_previous = 1.0

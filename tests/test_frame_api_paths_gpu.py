@@ -128,3 +128,39 @@ def test_more_rows_than_the_event_buffer(oracle_lib):
         if g == 255:
             assert len(b) > OWN_ROWS and ora.last["M"] <= 128
     assert [rc for rc, _, _ in rcs] == [0, 2, 0]
+
+
+def test_more_rows_than_the_event_buffer_with_a_text_file_open(oracle_lib, tmp_path):
+    """rc 2 with an event file open: the step-wise entry points finish the frame and its rows reach the file once, through the
+    same frame tail as the one-call frame's.  8 x 70 pixels stepping 0 -> 255 -> 128 with thresholds 0.02: more rows than
+    generate_events' device buffer holds, no more iterations than the scratch.  The twin's device buffer is grown beforehand, so
+    every frame of its is the one-call frame (rc 0): the same rows (the oracle's), counters and file."""
+    from v2e_amd import EventEmulator
+    frames = [np.full((8, 70), g, np.uint8) for g in (0, 0, 255, 128)]
+    ora = oracle_lib.OracleEmulator(rng_mode="philox", seed=3, **_kw(0.02))
+    ref = [ora.generate_events(f, DT * i) for i, f in enumerate(frames)]
+    assert len(ref[2]) > OWN_ROWS > len(ref[3]) > 0 and len(ref[2]) <= 8 * 70 * 512  # (every pixel makes the same events)
+
+    def run(name, grow_first):
+        emu = EventEmulator(device="cuda", rng_mode="philox", seed=3, max_iters=512, output_folder=str(tmp_path), dvs_text=name,
+                            **_kw(0.02))
+        rcs, rows = [], []
+        for i, f in enumerate(frames):
+            rows.append(emu.generate_events(f, DT * i))
+            if i == 0:
+                if grow_first:
+                    emu._engine.event_buffer(1 << 18)
+                eng_frame = emu._engine.frame
+                emu._engine.frame = lambda *args: rcs.append(eng_frame(*args)) or rcs[-1]
+        state = (emu.num_events_total, emu.num_events_on, emu.num_events_off, emu.t_previous, emu.frame_counter)
+        emu.cleanup()
+        lines = open(str(tmp_path / (name + ".txt")), "rb").read().split(b"\n")
+        return rows, [rc for rc, _, _ in rcs], state, [l for l in lines if not l.startswith(b"#")]
+
+    rows, rcs, state, lines = run("grown", False)
+    twin_rows, twin_rcs, twin_state, twin_lines = run("twin", True)
+    assert rcs == [0, 2, 0] and twin_rcs == [0, 0, 0]
+    for a, b, c in zip(rows, twin_rows, ref):
+        assert (a is None) == (b is None) == (c is None) and (a is None or (_same_rows(a, c) and _same_rows(b, c)))
+    assert state == twin_state == (len(ref[2]) + len(ref[3]), len(ref[2]), len(ref[3]), DT * 3, 4)
+    assert lines == twin_lines and len(lines) == state[0] + 1

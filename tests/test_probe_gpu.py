@@ -371,3 +371,24 @@ def test_video_to_events_records_across_runs_and_chunks(tmp_path, monkeypatch):
     b.emu.cleanup()
     with open(b.emu.SINGLE_PIXEL_STATES_FILENAME, "rb") as f:
         _same_series(pickle.load(f), st)
+
+
+def test_a_first_call_with_the_first_frame_alone_is_an_empty_run():
+    """The clip's first frame only initialises the state: a call that carries nothing else returns the empty handle -- no rows
+    (a [0, 4] device tensor with return_device), zero counts, the ten series with no sample of every probed pixel -- and the
+    clip goes on from there as if the frame had come with the next run."""
+    c = Case("defaults")
+    whole = c.emu()
+    ev, counts = whole.generate_events_batch(c.frames[:8], c.times[:8], probe_pixels=[(1, 2), (3, 4), (5, 6)])
+    emu = c.emu()
+    ev0, counts0 = emu.generate_events_batch(c.frames[:1], c.times[:1], probe_pixels=[(1, 2), (3, 4), (5, 6)])
+    assert ev0 is None and list(counts0) == [0] and (emu.num_events_total, emu.frame_counter) == (0, 1)
+    assert tuple(emu.last_probes) == SERIES and all(emu.last_probes[k].shape == (0, 3) for k in SERIES)
+    ev1, counts1 = emu.generate_events_batch(c.frames[1:8], c.times[1:8], probe_pixels=[(1, 2), (3, 4), (5, 6)])
+    assert np.array_equal(_rows(ev1), _rows(ev)) and list(counts1) == list(counts[1:])
+    for k in SERIES:
+        assert np.array_equal(emu.last_probes[k], whole.last_probes[k], equal_nan=True), k
+    h = c.emu().generate_events_batch_async(c.frames[:1], c.times[:1], return_device=True)
+    rows, counts2 = h.result()
+    assert torch.is_tensor(rows) and rows.is_cuda and tuple(rows.shape) == (0, 4) and list(counts2) == [0]
+    assert h.done is None and h.probes is None

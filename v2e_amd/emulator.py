@@ -1,5 +1,11 @@
 """Drop-in `EventEmulator` running the DVS pixel model on MI355X HIP kernels.
 
+This module holds the class itself: the reference's constructor surface and every attribute of an instance (declared in
+__init__, or in reset() where it is per clip), the parameter snapshot, the first frame, the per-frame path `generate_events`
+(tape replay and the one-call Philox frame), the centre-surround host arithmetic, and the entry points of device-resident runs,
+which validate their arguments and hand over to v2e_amd/runs.py.  The event files are v2e_amd/event_files.py, the research
+tooling (cv2 display, single-pixel recorder, probes) v2e_amd/model_states.py.
+
 Mirrors the public surface of the reference class (v2ecore/emulator.py:35-1059):
 same constructor signature (:86-117), `generate_events(new_frame, t_frame)` (:619),
 `set_dvs_params` (:513), `reset` (:558), `prepare_storage` (:374), `cleanup` (:402),
@@ -32,6 +38,7 @@ frames, csrc/csdvs.hip; in generate_events_batch too: the stepping loop is enque
 are supported.
 """
 import atexit
+import ctypes as C
 import logging
 import math
 import os
@@ -43,9 +50,11 @@ import weakref
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, event_files, model_states, runs
 from ._capi import EmuParams, RNG_PHILOX, RNG_TAPE
 from .engine import EmuEngine
+from .model_states import PIXEL_STATE_SERIES, append_pixel_states, probe_pixel_indices  # noqa: F401 (importable from here, as ever)
+from .runs import default_event_capacity  # noqa: F401
 
 logger = logging.getLogger(__name__)
 
@@ -141,89 +150,6 @@ def _cleanup_at_exit(ref):
         emu.cleanup()
 
 
-PIXEL_STATE_SERIES = ("time",) + _capi.PROBE_FIELD_NAMES  # the reference's ten series, in its order (emulator.py:287-294)
-
-
-def probe_pixel_indices(pixels, H, W, most=_capi.PROBE_MAX):
-    """[(a, b), ...] -- addressed as the reference's plane[a, b], row then column, like record_single_pixel_states -- as the
-    indices a * W + b v2e_emu_set_probes takes.  ValueError for more than `most` pixels, for anything that is not a pair of
-    integers and for a pixel outside the H x W array (no negative indices: an event row never carries one)."""
-    pixels = list(pixels)
-    if len(pixels) > most:
-        raise ValueError("at most %d pixels can be probed in one run, got %d" % (most, len(pixels)))
-    out = []
-    for px in pixels:
-        try:
-            a, b = px
-            a, b = int(a.__index__()), int(b.__index__())
-        except (TypeError, ValueError, AttributeError):
-            raise ValueError("a probed pixel is a pair of integers (row, column), got %r" % (px,))
-        if not (0 <= a < H and 0 <= b < W):
-            raise ValueError("probed pixel %r lies outside the %d x %d pixel array" % (px, H, W))
-        out.append(a * W + b)
-    return out
-
-
-def append_pixel_states(states, count, max_samples, times, block, pos_thres=None, neg_thres=None):
-    """What emulator.py:985-1009 does frame after frame, for the frames of one device-resident run: `block` [F, PROBE_FIELDS]
-    (one probe of v2e_emu_set_probes, the clip's very first frame not among them) and their frame times go to samples count,
-    count + 1, ... of the ten series while there is room; pos_thres / neg_thres: the Python-float thresholds, recorded instead of
-    the block's where the reference holds scalars (emulator.py:992-995).  Returns (new count, stop): stop when a frame came after
-    the series were full -- where the reference saves the file and ends the recording."""
-    F = len(times)
-    n = max(0, min(F, max_samples - count))
-    for k in range(count, count + n):
-        if k % 250 == 0:
-            logger.info(f'recorded {k} single pixel states')
-    sl = slice(count, count + n)
-    states['time'][sl] = np.asarray(times, dtype=np.float64)[:n]
-    for i, name in enumerate(_capi.PROBE_FIELD_NAMES):
-        states[name][sl] = block[:n, i]
-    if pos_thres is not None:
-        states['pos_thres'][sl] = pos_thres
-    if neg_thres is not None:
-        states['neg_thres'][sl] = neg_thres
-    return count + n, F > n
-
-
-def default_event_capacity(n_frames, H, W):
-    """Event rows a device-resident run of n_frames frames of H x W gets when no cap is given: 4 events per pixel and frame (the
-    reference never drops events; a run that exceeds this raises and leaves the instance unusable until reset()), bounded to
-    4 GiB of rows for very long runs."""
-    per_frame = max(4 * H * W, 1 << 16)
-    return per_frame * min(n_frames, max(64, (4 << 30) // (16 * per_frame)))
-
-
-class _PendingRun:
-    """Handle of an enqueued device-resident run (EventEmulator.generate_events_batch_async)."""
-
-    def __init__(self, emu, ev, recs, done, counts, start, return_device, empty, dts=None, ticket=None):
-        self.emu, self.ev, self.recs, self._done = emu, ev, recs, done
-        self.counts, self.start, self.return_device, self.empty, self.dts = counts, start, return_device, empty, dts
-        self.ticket = ticket  # pipelined runs (v2e_emu_run, RUN_PIPELINED): what result() waits for on the host (v2e_emu_run_wait)
-        self._res = None
-        self.probe_rec, self.probe_claim = False, 0  # the recorder's pixel is probe 0 of the run; the samples it will add
-        self.which = None     # the buffer set the run's rows and records are in
-        self.probes = None    # probe_pixels=...: the ten series of the probed pixels, float64 [F_run, P] each (after result())
-        self.probe_dev = None  # a probed run's device block [F_run][probes][PROBE_FIELDS], until result() reads it
-        self.frame0 = 0       # 0-based index of the run's first frame in the clip (the HDF5 frame_idx slot)
-
-    @property
-    def done(self):
-        """A torch event behind which the run's rows and records are final (for callers that order their own streams behind it)."""
-        if self._done is None and self.recs is not None:
-            self._done = self.emu._engine.run_done_event()
-        return self._done
-
-    def result(self):
-        if self._res is None:
-            if self.recs is None:
-                self._res = ((self.empty if self.return_device else None), self.counts)
-            else:
-                self._res = self.emu._finish_run(self)
-        return self._res
-
-
 class EventEmulator(object):
     """compute events based on the input frame (MI355X implementation)."""
 
@@ -235,7 +161,7 @@ class EventEmulator(object):
     MODEL_STATES = {'new_frame': gr, 'log_new_frame': lg, 'lp_log_frame': lg, 'scidvs_highpass': slg,
                     'photoreceptor_noise_arr': slg, 'cs_surround_frame': lg, 'c_minus_s_frame': slg,
                     'base_log_frame': slg, 'diff_frame': slg}
-    MAX_CHANGE_TO_TERMINATE_EULER_SURROUND_STEPPING = 1e-5
+    MAX_CHANGE_TO_TERMINATE_EULER_SURROUND_STEPPING = 1e-5  # emulator.py:52
     SINGLE_PIXEL_STATES_FILENAME = 'pixel-states.dat'
     SINGLE_PIXEL_MAX_SAMPLES = 10000
     SCIDVS_GAIN = 2
@@ -279,32 +205,45 @@ class EventEmulator(object):
             photoreceptor_noise_vrms: Optional[float] = None,
             tape_host_threads: Optional[int] = 1,
     ):
-        # research tooling (host pass-throughs, see the module docstring)
+        # what cleanup() reads, declared before anything below can raise: __del__ runs it on a half-built instance too
+        self.cs_steps_taken = []  # CSDVS (emulator.py:245-272): Euler steps each frame took; cleanup() reports and empties it
+        self._host_threads_prev = None  # what _limit_host_threads returned: not None while this instance counts as its user
+        self.video_writers = {}  # save_dvs_model_state: cv2.VideoWriter per shown state
+        self._sink_runs = []  # device-resident runs not yet in the event files / the recorder's series, oldest first (runs.py)
+        self.record_single_pixel_states = None  # the recorded pixel; None once the recording has ended
+        # event file writers are outside the hot path (emulator.py:312-346; event_files.py); None: closed
+        self.dvs_h5 = self.dvs_aedat2 = self.dvs_aedat4 = self.dvs_text = None
+        self.dvs_h5_dataset = self.frame_h5_dataset = self.frame_ts_dataset = self.frame_ev_idx_dataset = None
+        self._h5_stream = None  # side stream the HDF5 rows of device-resident runs are packed on
+
+        # research tooling (host pass-throughs, model_states.py)
         self.dont_show_list = []
         self.show_list = []
-        self.video_writers = {}
-        self._state_planes = None
+        self._state_planes = None  # three float64 planes k_count fills while states are shown or recorded
         self._cv2 = None
         self._show_warned = False
         if show_dvs_model_state is not None and len(show_dvs_model_state) == 1 and show_dvs_model_state[0] == 'all':
             logger.info(f'will show all model states that exist from {EventEmulator.MODEL_STATES.keys()}')  # emulator.py:365-368
             show_dvs_model_state = list(EventEmulator.MODEL_STATES.keys())
-        self.record_single_pixel_states = record_single_pixel_states  # emulator.py:279-300
-        self.single_pixel_sample_count = 0
-        if self.record_single_pixel_states is None:
-            self.single_pixel_states = None
-        else:
-            if not (type(self.record_single_pixel_states) is tuple):
-                raise ValueError(f'--record_single_pixel_states {self.record_single_pixel_states} should be a tuple, e.g. (10,20)')
-            if len(self.record_single_pixel_states) != 2:
-                raise ValueError(f'--record_single_pixel_states {self.record_single_pixel_states} should have two pixel addresses (x,y)')
-            for i in self.record_single_pixel_states:
+        if record_single_pixel_states is not None:  # emulator.py:279-300; checked before it is kept: cleanup() pickles for whatever is
+            if not (type(record_single_pixel_states) is tuple):
+                raise ValueError(f'--record_single_pixel_states {record_single_pixel_states} should be a tuple, e.g. (10,20)')
+            if len(record_single_pixel_states) != 2:
+                raise ValueError(f'--record_single_pixel_states {record_single_pixel_states} should have two pixel addresses (x,y)')
+            for i in record_single_pixel_states:
                 if not (type(i) is int):
-                    raise ValueError(f'--record_single_pixel_states {self.record_single_pixel_states} should have two '
+                    raise ValueError(f'--record_single_pixel_states {record_single_pixel_states} should have two '
                                      f'integer-value pixel addresses (x,y)')
-            self.single_pixel_states = {k: np.full(self.SINGLE_PIXEL_MAX_SAMPLES, np.nan) for k in (
-                'time', 'new_frame', 'base_log_frame', 'lp_log_frame', 'log_new_frame', 'pos_thres', 'neg_thres', 'diff_frame',
-                'final_neg_evts_frame', 'final_pos_evts_frame')}
+        self.record_single_pixel_states = record_single_pixel_states
+        self.single_pixel_sample_count = 0
+        self.single_pixel_states = None if self.record_single_pixel_states is None else {
+            k: np.full(self.SINGLE_PIXEL_MAX_SAMPLES, np.nan) for k in PIXEL_STATE_SERIES}
+        self.last_probes = None  # generate_events_batch(probe_pixels=...): the series of the last such call
+
+        # device-resident runs (runs.py); what is per clip is in reset()
+        self._async_flip = 0  # the buffer set (0 / 1) the next asynchronous run writes
+        self._blocking_lengths = {}  # run length -> blocking calls seen: the hipGraph is built from the second on
+        self._refr_mostly_on = False  # the refractory rule was active in most frames of the last run read
 
         self.no_events_warning_count = 0
         logger.info("ON/OFF log_e temporal contrast thresholds: {} / {} +/- {}".format(
@@ -324,8 +263,8 @@ class EventEmulator(object):
         self.shot_noise_rate_hz = shot_noise_rate_hz
         self.photoreceptor_noise = bool(photoreceptor_noise)
         self.photoreceptor_noise_vrms = photoreceptor_noise_vrms  # None: computed like emulator_utils.py:177-290
-        self._pn_last_rate = None
-        self.photoreceptor_noise_arr = None
+        self._pn_vrms = 0.0  # the amplitude in force (_prepare_pnoise)
+        self._pn_plane = None  # photoreceptor_noise_arr's padded device plane, from the first noisy frame on
         if self.photoreceptor_noise and (shot_noise_rate_hz == 0 or cutoff_hz == 0):  # emulator.py:196-204 (v2e_quit)
             logger.error('--photoreceptor_noise needs a finite --shot_noise_rate_hz and --cutoff_hz')
             raise SystemExit(1)
@@ -340,14 +279,13 @@ class EventEmulator(object):
         self.label_signal_noise = label_signal_noise
         self.log_input = bool(hdr)  # emulator.py:304: frames are log-encoded already
         self.scidvs = bool(scidvs)  # emulator.py:307-309: nonlinear CR high-pass amplified log intensity
-        self.scidvs_highpass = self.scidvs_previous_photo = self.scidvs_tau_arr = None
+        self._sc_planes = self._sc_tau = None  # the padded device planes behind scidvs_highpass, scidvs_previous_photo, scidvs_tau_arr
         # CSDVS (emulator.py:245-272)
         self.cs_steps_warning_printed = False
-        self.cs_steps_taken = []
         self.cs_alpha_warning_printed = False
         self.cs_tau_p_ms = cs_tau_p_ms
         self.cs_lambda_pixels = cs_lambda_pixels
-        self.cs_surround_frame = None
+        self._cs_planes = None  # [surround, ping-pong scratch, the coming frame's lp_log_frame], from the first frame on
         self.csdvs_enabled = cs_lambda_pixels is not None
         if self.csdvs_enabled:
             self.cs_tau_h_ms = 0 if (cs_tau_p_ms is None or cs_tau_p_ms == 0) else cs_tau_p_ms / (cs_lambda_pixels ** 2)
@@ -360,7 +298,6 @@ class EventEmulator(object):
             raise ValueError("rng_mode must be 'tape' or 'philox', got %r" % (self.rng_mode,))
         self.shuffle = bool(shuffle)
         self._tape = tape if tape is not None else _TorchTape()
-        self._host_threads_prev = None
         if self.rng_mode == "tape":
             self._host_threads_prev = _limit_host_threads(tape_host_threads)
         self._max_iters = max_iters
@@ -369,69 +306,20 @@ class EventEmulator(object):
             np.random.seed(seed)
             random.seed(seed)
 
-        # event file writers are outside the hot path: pass through to the reference's own
-        # writer classes when they are importable (emulator.py:312-346)
-        self.dvs_h5 = self.dvs_aedat2 = self.dvs_aedat4 = self.dvs_text = None
-        self.dvs_h5_dataset = self.frame_h5_dataset = self.frame_ts_dataset = self.frame_ev_idx_dataset = None
-        self._open_writers(dvs_h5, dvs_aedat2, dvs_aedat4, dvs_text)
+        event_files.open_sinks(self, dvs_h5, dvs_aedat2, dvs_aedat4, dvs_text)
 
         self._engine: Optional[EmuEngine] = None
-        self._thres_scalar = None
+        self._thres_scalar = None  # (pos, neg) as Python floats, as they were when the first frame drew the planes
+        self._thres_is_scalar = False  # ... and whether they stayed scalars (sigma_thres == 0)
+        self._idx_pin = self._idx_dev = None  # tape mode: pinned / device staging of a frame's shuffle indices
         # emulator.py:296 registers cleanup with atexit.  Through a weak reference here: a bound method would keep every emulator -- and
         # the gigabytes of device scratch a 1280x720 one holds -- alive until the process ends; one that is dropped is cleaned up then
         # (__del__), one that is still alive at exit by the hook
         atexit.register(_cleanup_at_exit, weakref.ref(self))
 
     # ------------------------------------------------------------- plumbing
-    def _open_writers(self, dvs_h5, dvs_aedat2, dvs_aedat4, dvs_text):
-        """Event file sinks (emulator.py:312-346).  AEDAT-2.0 and text: v2e_amd.sinks writers fed from the device-resident
-        event buffer (integer conversion on the GPU, byte-identical to the reference writers).  HDF5: the reference's own
-        layout through h5py (rows converted on the GPU).  AEDAT-4: v2e_amd.sinks.HostAEDat4Output over the third-party
-        dv_processing package (as the reference's writer is), or any writer object the caller passes as `dvs_aedat4`."""
-        if not (dvs_h5 or dvs_aedat2 or dvs_aedat4 or dvs_text):
-            return
-
-        def suffixed(name, suffix):  # v2e_utils.checkAddSuffix
-            return name if name.endswith(suffix) else name + suffix
-
-        folder = self.output_folder or ""
-        if dvs_h5:
-            try:
-                import h5py
-            except ImportError as e:
-                raise NotImplementedError("dvs_h5 needs h5py: %s" % e)
-            self.dvs_h5 = h5py.File(suffixed(os.path.join(folder, dvs_h5), '.h5'), "w")
-            self.dvs_h5_dataset = self.dvs_h5.create_dataset(
-                name="events", shape=(0, 4), maxshape=(None, 4), dtype="uint32", compression="gzip")
-        if dvs_aedat2:
-            from .sinks import DeviceAEDat2Output
-            self.dvs_aedat2 = DeviceAEDat2Output(suffixed(os.path.join(folder, dvs_aedat2), '.aedat'),
-                                                 output_width=self.output_width, output_height=self.output_height,
-                                                 label_signal_noise=self.label_signal_noise)
-        if dvs_text:
-            from .sinks import DeviceTextOutput
-            self.dvs_text = DeviceTextOutput(suffixed(os.path.join(folder, dvs_text), '.txt'),
-                                             label_signal_noise=self.label_signal_noise)
-        if dvs_aedat4:
-            if hasattr(dvs_aedat4, "appendEvents"):  # a caller-supplied writer object
-                self.dvs_aedat4 = dvs_aedat4
-            else:
-                from .sinks import HostAEDat4Output  # over dv_processing; NotImplementedError where that is absent
-                self.dvs_aedat4 = HostAEDat4Output(suffixed(os.path.join(folder, dvs_aedat4), '.aedat4'))
-
     def prepare_storage(self, n_frames, frame_ts):  # emulator.py:374-400
-        if self.dvs_h5:
-            self.frame_h5_dataset = self.dvs_h5.create_dataset(
-                name="frame", shape=(n_frames, self.output_height, self.output_width), dtype="uint8",
-                compression="gzip")
-            frame_ts_arr = np.array(frame_ts, dtype=np.float32) * 1e6
-            self.frame_ts_dataset = self.dvs_h5.create_dataset(
-                name="frame_ts", shape=(n_frames,), data=frame_ts_arr.astype(np.uint32), dtype="uint32",
-                compression="gzip")
-            self.frame_ev_idx_dataset = self.dvs_h5.create_dataset(
-                name="frame_idx", shape=(n_frames,), dtype="uint64", compression="gzip")
-        else:
-            self.frame_h5_dataset = self.frame_ts_dataset = self.frame_ev_idx_dataset = None
+        event_files.prepare_storage(self, n_frames, frame_ts)
 
     def __del__(self):
         try:
@@ -440,61 +328,51 @@ class EventEmulator(object):
             pass
 
     def cleanup(self):  # emulator.py:402-429
-        if len(getattr(self, "cs_steps_taken", ())) > 1:
+        """Order: the held device-resident runs are finished and written (event files, recorder series, their CSDVS steps); the
+        CSDVS statistics line; the thread override; the AVI writers; the recorder's pickle; the event files.  The held runs come
+        first -- before the statistics line, where the reference has no such step -- because a run's Euler steps reach
+        cs_steps_taken only when its result is read: logged first, the line would miss them.  Everything it closes it also forgets
+        (cs_steps_taken is emptied once reported, the thread override, the writers, the recorder, the sinks), so a second call --
+        the atexit hook or __del__ after the caller's own -- finds nothing to do: no second statistics line, no file touched."""
+        # every run enqueued while the sinks were open (or the recorder on) reaches them before they close -- and first of all, so
+        # that the statistics below include the Euler steps of the runs read here
+        runs.write_held(self)
+        if len(self.cs_steps_taken) > 1:
             logger.info(f'CSDVS steps statistics: mean+std= {np.mean(self.cs_steps_taken):.0f} + {np.std(self.cs_steps_taken):.0f} '
                         f'(median= {np.median(self.cs_steps_taken):.0f})')
-        if getattr(self, "_host_threads_prev", None) is not None:
+            self.cs_steps_taken = []
+        if self._host_threads_prev is not None:
             _release_host_threads()
             self._host_threads_prev = None
-        for name, vw in list(getattr(self, "video_writers", {}).items()):  # emulator.py:424-426
+        for name, vw in list(self.video_writers.items()):  # emulator.py:424-426
             logger.info(f'closing video AVI {name}')
             try:
                 vw.release()
             except Exception:
                 pass
-        if getattr(self, "video_writers", None):
-            self.video_writers = {}
-        self._write_held_runs()  # every run enqueued while the sinks were open (or the recorder on) reaches them before they close
-        if getattr(self, "record_single_pixel_states", None) is not None:  # emulator.py:428-429
-            self.save_recorded_single_pixel_states()
-            self.record_single_pixel_states = None
-        for w in ("dvs_h5", "dvs_aedat2", "dvs_aedat4", "dvs_text"):
-            o = getattr(self, w, None)
-            if o is not None:
-                try:
-                    o.close()
-                except Exception:
-                    pass
-                setattr(self, w, None)
+        self.video_writers = {}
+        if self.record_single_pixel_states is not None:  # emulator.py:428-429
+            model_states.end_recording(self)
+        event_files.close(self)
 
-    def set_dvs_params(self, model: str):  # emulator.py:513-556
-        if model == 'clean':
-            self.pos_thres = 0.2
-            self.neg_thres = 0.2
-            self.sigma_thres = 0.02
-            self.cutoff_hz = 0
-            self.leak_rate_hz = 0
-            self.leak_jitter_fraction = 0
-            self.noise_rate_cov_decades = 0
-            self.shot_noise_rate_hz = 0
-            self.refractory_period_s = 0
-        elif model == 'noisy':
-            self.pos_thres = 0.2
-            self.neg_thres = 0.2
-            self.sigma_thres = 0.05
-            self.cutoff_hz = 30
-            self.leak_rate_hz = 0.1
-            self.shot_noise_rate_hz = 5.0
-            self.refractory_period_s = 0
-            self.leak_jitter_fraction = 0.1
-            self.noise_rate_cov_decades = 0.1
-        else:
+    DVS_PARAMS = {  # emulator.py:513-556
+        'clean': dict(pos_thres=0.2, neg_thres=0.2, sigma_thres=0.02, cutoff_hz=0, leak_rate_hz=0, leak_jitter_fraction=0,
+                      noise_rate_cov_decades=0, shot_noise_rate_hz=0, refractory_period_s=0),
+        'noisy': dict(pos_thres=0.2, neg_thres=0.2, sigma_thres=0.05, cutoff_hz=30, leak_rate_hz=0.1, shot_noise_rate_hz=5.0,
+                      refractory_period_s=0, leak_jitter_fraction=0.1, noise_rate_cov_decades=0.1)}
+
+    def set_dvs_params(self, model: str):
+        if model not in self.DVS_PARAMS:
             logger.warning("dvs_params {} not known: Using commandline assigned options".format(model))
+        for name, value in self.DVS_PARAMS.get(model, {}).items():
+            setattr(self, name, value)
 
     def reset(self):  # emulator.py:558-578
-        self._write_held_runs()  # runs still held for the open sinks are written first (dropped if a run failed)
-        self._failed = None
-        self._async_slots = {}  # handles of runs enqueued before the reset are no longer collected on the caller's behalf
+        runs.write_held(self)  # runs still held for the open sinks are written first (dropped if a run failed)
+        self._failed = None  # the error text of a device-resident run that failed: the instance refuses frames until the next reset()
+        # buffer set -> weakref of the run that last used it; handles of runs enqueued before the reset are no longer collected on
+        # the caller's behalf
+        self._async_slots = {}
         self.num_events_total = 0
         self.num_events_on = 0
         self.num_events_off = 0
@@ -503,6 +381,7 @@ class EventEmulator(object):
         self.lp_log_frame = None
         self.base_log_frame = None
         self.diff_frame = None
+        self.c_minus_s_frame = None
         self.frame_counter = 0
         self.timestamp_mem = None
         self.noise_rate_array = None
@@ -513,9 +392,15 @@ class EventEmulator(object):
         self._initialized = False
 
     # ------------------------------------------------------------- parameters
+    def _raise_if_failed(self, why=""):
+        if self._failed:
+            raise _capi.V2EAmdError("a previous device-resident run failed (%s); %scall reset()" % (self._failed, why))
+
     def _params(self) -> EmuParams:
         """Snapshot the (mutable) attributes into the C struct, every call."""
         P = EmuParams()
+        # the state planes are float64 iff the reference's are: with the low-pass on, or log-encoded input.  (The one statement of
+        # the rule: the first frame allocates by P.f64_state, later ones compare it with the engine's.)
         P.f64_state = 1 if (self.cutoff_hz > 0 or self.log_input) else 0
         P.log_input = 1 if self.log_input else 0
         P.scalar_thres = 1 if self._thres_scalar is not None and self._thres_is_scalar else 0
@@ -533,7 +418,7 @@ class EventEmulator(object):
         # photoreceptor noise replaces the shot-event generator and its base reset (emulator.py:893, 940)
         P.shot_noise_rate_hz = 0.0 if self.photoreceptor_noise else float(self.shot_noise_rate_hz)
         P.photoreceptor_noise = 1 if self.photoreceptor_noise else 0
-        P.photoreceptor_noise_vrms = float(getattr(self, "_pn_vrms", 0.0) or 0.0)
+        P.photoreceptor_noise_vrms = float(self._pn_vrms)
         P.shot_noise_inten_factor = float(self.SHOT_NOISE_INTEN_FACTOR)
         if P.scalar_thres:  # emulator.py:475-478 with Python-float thresholds
             P.pos_pre_scalar = float(torch.div(self.pos_thres_nominal, P.pos_thres_scalar))
@@ -565,12 +450,12 @@ class EventEmulator(object):
             self.pos_thres, self.neg_thres = prev
         self._thres_scalar = (float(self.pos_thres), float(self.neg_thres))
         self._thres_is_scalar = not (self.sigma_thres > 0)
-        eng.alloc_state(self.cutoff_hz > 0 or self.log_input)
         P = self._params()
+        eng.alloc_state(bool(P.f64_state))
         tp = tn = nr = None
         sc_tau_host = None
         if self.scidvs:  # two more state planes + per-pixel time constants (emulator.py:480-483, 719-722)
-            sd = torch.float64 if (self.cutoff_hz > 0 or self.log_input) else torch.float32  # zeros_like(lp_log_frame)
+            sd = torch.float64 if eng.f64_state else torch.float32  # zeros_like(lp_log_frame)
             self._sc_planes = [torch.zeros((1, eng.npx_pad), dtype=sd, device=eng.device) for _ in range(2)]
             self._sc_tau = torch.zeros((1, eng.npx_pad), dtype=torch.float32, device=eng.device)
             _capi.check(eng.lib.v2e_emu_set_scidvs(eng._h, self._sc_planes[0].data_ptr(), self._sc_planes[1].data_ptr(),
@@ -602,12 +487,10 @@ class EventEmulator(object):
             self.cs_surround_frame = eng.plane(self._cs_planes[0])
         else:
             eng.set_csdvs(None)
-        if self._wants_states():
+        self._state_planes = None
+        if model_states.wants_states(self):
             self._state_planes = [torch.zeros((1, eng.npx_pad), dtype=torch.float64, device=eng.device) for _ in range(3)]
-            eng.set_model_state_planes(self._state_planes)
-        else:
-            self._state_planes = None
-            eng.set_model_state_planes(None)
+        eng.set_model_state_planes(self._state_planes)
         # public state attributes, as [H,W] device views
         self.lp_log_frame = eng.plane(eng.lp)
         self.base_log_frame = eng.plane(eng.base)
@@ -627,11 +510,7 @@ class EventEmulator(object):
         new_frame: np.ndarray or torch tensor [height, width]; t_frame: seconds.
         Returns np.ndarray [N,4] float32 rows [t, x, y, p(+1/-1)] or None.
         """
-        return self._generate_events(new_frame, t_frame)
-
-    def _generate_events(self, new_frame, t_frame):
-        if getattr(self, "_failed", None):
-            raise _capi.V2EAmdError("a previous device-resident run failed (%s); call reset()" % self._failed)
+        self._raise_if_failed()
         if self.frame_h5_dataset is not None:
             fr = new_frame.detach().cpu().numpy() if torch.is_tensor(new_frame) else np.asarray(new_frame)
             self.frame_h5_dataset[self.frame_counter] = fr.astype(np.uint8)
@@ -647,7 +526,7 @@ class EventEmulator(object):
         # Philox mode after the first frame: the whole frame is ONE C call (v2e_emu_frame), the host frame goes through
         # the handle's pinned staging instead of a torch tensor
         fast = self._initialized and self.rng_mode == "philox" and not self.photoreceptor_noise and not self.csdvs_enabled \
-            and not self._wants_states()
+            and not model_states.wants_states(self)
         host_frame = None
         if fast and isinstance(new_frame, np.ndarray) and new_frame.dtype in (np.uint8, np.float32, np.float64):
             host_frame = np.ascontiguousarray(new_frame)
@@ -673,41 +552,19 @@ class EventEmulator(object):
             rc, out8, events = eng.frame(P, host_frame if host_frame is not None else frame_dev, t_prev, t_frame, fidx, ev)
             n_events, n_on, n_off, n_signal, M = (int(out8[k]) for k in range(5))
             if rc == 0:
-                if M > 100:
-                    logger.warning(f'Too many events generated for this frame: num_iter={M}>100 events')
-                if M == 0 and self.no_events_warning_count < 100:
-                    logger.warning(f'no signal events generated for frame #{self.frame_counter:,} at t={t_frame:.4f}s')
-                    self.no_events_warning_count += 1
-                self.num_events_on += n_on
-                self.num_events_off += n_off
-                self.num_events_total += n_events
-                if events is not None:
-                    self._write_events(events, n_signal, events_dev=ev[0, :n_events])
-                if self.frame_ev_idx_dataset is not None:
-                    self.frame_ev_idx_dataset[self.frame_counter - 1] = self.dvs_h5_dataset.shape[0]
-                self.t_previous = t_frame
-                return events
+                return self._frame_done(new_frame, t_frame, M, n_events, n_on, n_off, n_signal, events, ev)
             # rc 1: more iterations than the scratch holds; rc 2: more rows than the buffer: the frame is counted, the general
             # path below grows what is needed and finishes it
             counted = True
             if frame_dev is None:
                 frame_dev = eng.to_device_frame(new_frame)
 
-        pn_draw = None
         if self.photoreceptor_noise:  # emulator.py:694-703
-            if self.photoreceptor_noise_arr is None:  # zeros_like(lp_log_frame) on the first frame (emulator.py:684)
-                self._pn_plane = torch.zeros((1, eng.npx_pad), dtype=torch.float64, device=dev)
-                self.photoreceptor_noise_arr = eng.plane(self._pn_plane)
-            rate = 1.0 / (t_frame - t_prev)
-            if self.photoreceptor_noise_vrms is not None:
-                self._pn_vrms = float(self.photoreceptor_noise_vrms)
-            elif self._pn_last_rate is None or abs(rate / self._pn_last_rate - 1) >= 0.1:  # emulator_utils.py:217-220
-                self._pn_vrms = photoreceptor_noise_vrms(self.shot_noise_rate_hz, self.cutoff_hz, rate, self.pos_thres_nominal,
-                                                         self.neg_thres_nominal, self.sigma_thres)
-                self._pn_last_rate = rate
+            self._prepare_pnoise(eng, [1.0 / (t_frame - t_prev)])
             P = self._params()
-            if tape:
-                pn_draw = _as_f32_tensor(self._tape.randn((H, W))).to(dev)  # before the leak draw, as in the reference
+            # the tape's draw comes before the leak draw, as in the reference; set_pnoise keeps its address for count(): the tensor
+            # has to live until then
+            pn_draw = _as_f32_tensor(self._tape.randn((H, W))).to(dev) if tape else None
             eng.set_pnoise(self._pn_plane, pn_draw)
         leak = None
         if tape and self.leak_rate_hz > 0:
@@ -717,11 +574,9 @@ class EventEmulator(object):
         if not counted:
             eng.count(P, frame_dev, [t_prev], [t_frame], fidx, leak_randn=leak)
         if self._state_planes is not None:
-            self._after_count_states(new_frame, t_frame)
+            model_states.show_states(self, new_frame, t_frame)
         rec = eng.read_rec(fidx)[0]
         M = int(rec.max_events)
-        if M > 100:
-            logger.warning(f'Too many events generated for this frame: num_iter={M}>100 events')
         eng.reserve_iters(M)
         n = M if M > 0 else 1
         ts_dev = None
@@ -729,17 +584,17 @@ class EventEmulator(object):
             ts_step = (t_frame - t_prev) / n
             ts = self._tape.linspace(t_prev + ts_step, t_frame, n)
             ts_dev = _as_f32_tensor(ts).to(dev).view(1, n)
-        if M == 0 and self.no_events_warning_count < 100:
-            logger.warning(f'no signal events generated for frame #{self.frame_counter:,} at t={t_frame:.4f}s')
-            self.no_events_warning_count += 1
 
         eng.rank(P, fidx, ts_dev)
         itc = eng.read_iter_counts(fidx, M)[0]  # [M+1][2]; last row = shot pair
-        perms = []
+        perms = []  # tape mode: (iteration's first row, its randperm) of every non-empty iteration
         if tape:
+            row = 0
             for i in range(M):
                 n_i = int(itc[i, 0]) + int(itc[i, 1])
-                perms.append(self._tape.randperm(n_i, fidx, i) if n_i > 0 else None)
+                if n_i > 0:
+                    perms.append((row, self._tape.randperm(n_i, fidx, i)))
+                row += n_i
             if self.shot_noise_rate_hz > 0 and not self.photoreceptor_noise:
                 u = _as_f32_tensor(self._tape.rand((H, W))).to(dev)
                 eng.shot(P, frame_dev, fidx, u)
@@ -753,22 +608,17 @@ class EventEmulator(object):
         events = None
         ev = eng.event_buffer(max(n_events, 1))
         eng.emit(P, fidx, ev, ts_dev, ev_offset0=[0])
-        if tape and n_signal > 0 and any(q is not None for q in perms):
+        if n_signal > 0 and perms:
             # events_curr_iter[idx] for every iteration (emulator.py:868-869) as ONE gather: the per-iteration
             # permutations, offset to absolute rows, in one pinned upload and one launch
             if eng._events_tmp is None or eng._events_tmp.shape != ev.shape:
                 eng._events_tmp = torch.empty_like(ev)
             out = eng._events_tmp
             idx_all = np.empty(n_signal, dtype=np.int32)
-            row = 0
-            for i in range(M):
-                n_i = int(itc[i, 0]) + int(itc[i, 1])
-                if n_i > 0:
-                    idx = perms[i]
-                    idx = idx.numpy() if torch.is_tensor(idx) else np.asarray(idx)
-                    np.add(idx, row, out=idx_all[row:row + n_i], casting="unsafe")
-                row += n_i
-            pin = getattr(self, "_idx_pin", None)
+            for row, idx in perms:  # (the shot pass in between leaves the iterations' counts as they were)
+                idx = idx.numpy() if torch.is_tensor(idx) else np.asarray(idx)
+                np.add(idx, row, out=idx_all[row:row + len(idx)], casting="unsafe")
+            pin = self._idx_pin
             if pin is None or pin.numel() < n_signal:
                 cap_n = max(n_signal, 1 << 16) * 2
                 self._idx_pin = pin = torch.empty(cap_n, dtype=torch.int32).pin_memory()
@@ -784,211 +634,58 @@ class EventEmulator(object):
         if n_events > 0:
             events = ev[0, :n_events].cpu().numpy()
 
+        return self._frame_done(new_frame, t_frame, M, n_events, n_on, n_off, n_signal, events, ev)
+
+    def _frame_done(self, new_frame, t_frame, M, n_events, n_on, n_off, n_signal, events, ev):
+        """The tail of every frame after the first, whichever path computed it: the reference's two warnings (emulator.py:776-777,
+        805-807), the counters, the event files, the recorder, t_previous.  events: the frame's host rows or None; ev: the device
+        buffer they are the first n_events rows of."""
+        if M > 100:
+            logger.warning(f'Too many events generated for this frame: num_iter={M}>100 events')
+        if M == 0 and self.no_events_warning_count < 100:
+            logger.warning(f'no signal events generated for frame #{self.frame_counter:,} at t={t_frame:.4f}s')
+            self.no_events_warning_count += 1
         self.num_events_on += n_on
         self.num_events_off += n_off
         self.num_events_total += n_events
-
         if events is not None:
-            self._write_events(events, n_signal, events_dev=ev[0, :n_events])
-        if self.frame_ev_idx_dataset is not None:
+            event_files.write_frame(self, events, n_signal, events_dev=ev[0, :n_events])
+        if self.frame_ev_idx_dataset is not None:  # emulator.py:979-983: where the frame's events end
             self.frame_ev_idx_dataset[self.frame_counter - 1] = self.dvs_h5_dataset.shape[0]
-        if self.record_single_pixel_states is not None:
-            self._record_single_pixel(new_frame, t_frame, events, n_signal)
+        if self.record_single_pixel_states is not None:  # (never on the one-call Philox frame)
+            model_states.record_pixel(self, new_frame, t_frame, events, n_signal)
         self.t_previous = t_frame
         return events
 
-    # ------------------------------------------------------------- research tooling (host pass-throughs)
-    def _wants_states(self):
-        return self.show_dvs_model_state is not None or self.record_single_pixel_states is not None
-
-    def _after_count_states(self, new_frame, t_frame):
-        """The attributes the reference holds at emulator.py:756 (after the leak, before the events), as device views; then
-        emulator.py:756-767: show / save the requested ones."""
-        eng = self._engine
-        sd = torch.float64 if eng.f64_state else torch.float32
-        self.new_frame = new_frame
-        self.log_new_frame = eng.plane(self._state_planes[0]).to(torch.float32)  # lin_log returns float32 (emulator_utils.py:45)
-        self.c_minus_s_frame = eng.plane(self._state_planes[1]).to(sd) if self.csdvs_enabled else None
-        self.diff_frame = eng.plane(self._state_planes[2]).to(sd)
-        if self.show_dvs_model_state is None:
+    def _prepare_pnoise(self, eng, rates):
+        """emulator.py:694-703 before the frames whose sample rates (1 / interval) are `rates`, one for generate_events, a run's
+        for a device-resident run: the noise plane, created on the first such frame (zeros_like(lp_log_frame), emulator.py:684; it
+        stays on the device), and the amplitude.  The reference recomputes the amplitude when the sample rate has moved by 10 % from
+        the rate it was last computed for (emulator_utils.py:217-220); inside one device-resident run the amplitude is one
+        number, so every frame of the run must stay within 10 % of the rate that number belongs to."""
+        if self.photoreceptor_noise_arr is None:
+            self._pn_plane = torch.zeros((1, eng.npx_pad), dtype=torch.float64, device=eng.device)
+            self.photoreceptor_noise_arr = eng.plane(self._pn_plane)
+        if self.photoreceptor_noise_vrms is not None:
+            self._pn_vrms = float(self.photoreceptor_noise_vrms)
             return
-        cv2 = self._host_cv2()
-        for s in self.show_dvs_model_state:
-            if s in self.dont_show_list:
-                continue
-            f = getattr(self, s, None)
-            if f is None:
-                logger.error(f'{s} does not exist so we cannot show it')
-                self.dont_show_list.append(s)
-            elif cv2 is not None:
-                self._show(f, s)
-        if cv2 is not None:
-            try:
-                k = cv2.waitKey(30)
-            except Exception:
-                k = -1
-            if k == 27 or k == ord('x'):
-                raise SystemExit(0)  # v2e_quit()
 
-    def _host_cv2(self):
-        if self._cv2 is None and not self._show_warned:
-            try:
-                import cv2
-                if not callable(getattr(cv2, "imshow", None)):
-                    raise ImportError("cv2 has no imshow")
-                self._cv2 = cv2
-            except Exception as e:
-                logger.warning("v2e_amd.EventEmulator: show_dvs_model_state / save_dvs_model_state need OpenCV on the host (%s): "
-                               "nothing is displayed or saved; the state planes stay readable as attributes (%s)", e,
-                               ", ".join(self.show_dvs_model_state))
-                self._show_warned = True
-        return self._cv2
+        def moved(rate):
+            return abs(rate / self._pn_last_rate - 1) >= 0.1
 
-    def _show(self, inp, name):
-        """emulator.py:580-617: normalise by MODEL_STATES[name], show, and append to <name>.avi with save_dvs_model_state."""
-        cv2 = self._cv2
-        img = np.array(inp.detach().cpu().numpy() if torch.is_tensor(inp) else inp, dtype=np.float64)
-        (lo, hi) = EventEmulator.MODEL_STATES[name]
-        img = (img - lo) / (hi - lo)
-        try:
-            cv2.namedWindow(name, cv2.WINDOW_NORMAL)
-            if name not in self.show_list:
-                self.show_list.append(name)
-                if self.save_dvs_model_state:
-                    fn = os.path.join(self.output_folder or "", name + '.avi')
-                    self.video_writers[name] = cv2.VideoWriter(fn, cv2.VideoWriter_fourcc(*'XVID'), 30,
-                                                               (int(self.output_width or img.shape[1]),
-                                                                int(self.output_height or img.shape[0])))
-            for org, col in (((0, img.shape[0]), (0, 0, 0)), ((1, img.shape[0] - 1), (255, 255, 255))):
-                cv2.putText(img, f'fr:{self.frame_counter} t:{self.t_previous:.4f}s', org=org, fontScale=1.3, color=col,
-                            fontFace=cv2.FONT_HERSHEY_PLAIN, thickness=1)
-            cv2.imshow(name, img)
-            if self.save_dvs_model_state:
-                g = (img * 255).astype(np.uint8)
-                self.video_writers[name].write(np.ascontiguousarray(np.repeat(g[:, :, None], 3, axis=2)))
-        except Exception as e:  # no display
-            logger.warning("v2e_amd.EventEmulator: cannot show %s (%s)", name, e)
-            self.dont_show_list.append(name)
-
-    def _record_single_pixel(self, new_frame, t_frame, events, n_signal):
-        """emulator.py:985-1009.  The index tuple addresses the [H, W] planes as the reference's does (plane[a, b]); the
-        final per-pixel ON / OFF counts are the frame's signal events at that pixel (what final_pos/neg_evts_frame hold)."""
-        ij = self.record_single_pixel_states
-        if self.single_pixel_sample_count < self.SINGLE_PIXEL_MAX_SAMPLES:
-            k = self.single_pixel_sample_count
-            if k % 250 == 0:
-                logger.info(f'recorded {k} single pixel states')
-            st = self.single_pixel_states
-            st['time'][k] = t_frame
-            st['new_frame'][k] = float(new_frame[ij])
-            st['base_log_frame'][k] = float(self.base_log_frame[ij])
-            st['lp_log_frame'][k] = float(self.lp_log_frame[ij])
-            st['log_new_frame'][k] = float(self.log_new_frame[ij])
-            st['pos_thres'][k] = self.pos_thres if type(self.pos_thres) is float else float(self.pos_thres[ij])
-            st['neg_thres'][k] = self.neg_thres if type(self.neg_thres) is float else float(self.neg_thres[ij])
-            st['diff_frame'][k] = float(self.diff_frame[ij])
-            on = off = 0
-            if events is not None and n_signal > 0:
-                sig = events[:n_signal]
-                here = (sig[:, 2] == ij[0]) & (sig[:, 1] == ij[1])  # rows are [t, x = column, y = row, p]
-                on = int(np.count_nonzero(here & (sig[:, 3] > 0)))
-                off = int(np.count_nonzero(here & (sig[:, 3] < 0)))
-            st['final_neg_evts_frame'][k] = off
-            st['final_pos_evts_frame'][k] = on
-            self.single_pixel_sample_count += 1
-        else:
-            self.save_recorded_single_pixel_states()
-            self.record_single_pixel_states = None
+        if self._pn_last_rate is None or moved(rates[0]):
+            self._pn_vrms = photoreceptor_noise_vrms(self.shot_noise_rate_hz, self.cutoff_hz, rates[0], self.pos_thres_nominal,
+                                                     self.neg_thres_nominal, self.sigma_thres)
+            self._pn_last_rate = rates[0]
+        if any(moved(r) for r in rates):
+            raise ValueError("photoreceptor_noise: the frame interval moves by more than 10 % from the rate the noise "
+                             "amplitude was computed for inside this run; split the run there (or use generate_events "
+                             "per frame)")
 
     def save_recorded_single_pixel_states(self):  # emulator.py:431-437
-        import pickle
-        try:
-            with open(self.SINGLE_PIXEL_STATES_FILENAME, 'wb') as outfile:
-                pickle.dump(self.single_pixel_states, outfile, protocol=pickle.HIGHEST_PROTOCOL)
-                logger.info(f'saved single pixel states with {self.single_pixel_sample_count} samples to '
-                            f'{self.SINGLE_PIXEL_STATES_FILENAME}')
-        except Exception as e:
-            logger.error(f'could not save pickled pixel states, got {e}')
-
-    def _write_events(self, events, n_signal, events_dev=None):
-        """emulator.py:953-977: append this frame's events to the open sinks.  The integer conversions of the HDF5 rows
-        (emulator.py:957-960), the AEDAT-2.0 words and the text columns run on the GPU on the device-resident rows."""
-        if not (self.dvs_h5 is not None or self.dvs_aedat2 is not None or self.dvs_aedat4 is not None or self.dvs_text is not None):
-            return
-        ev_dev = events_dev if events_dev is not None else torch.from_numpy(np.ascontiguousarray(events, dtype=np.float32)).to(
-            self._engine.device)
-        sig = n_signal if self.label_signal_noise else None
-        if self.dvs_h5 is not None:
-            from .sinks import pack_h5
-            temp = pack_h5(ev_dev).cpu().numpy().view(np.uint32)
-            self.dvs_h5_dataset.resize(self.dvs_h5_dataset.shape[0] + temp.shape[0], axis=0)
-            self.dvs_h5_dataset[-temp.shape[0]:] = temp
-        if self.dvs_aedat2 is not None:
-            self.dvs_aedat2.appendEvents(ev_dev, n_signal=sig)
-        if self.dvs_aedat4 is not None:
-            label = None
-            if self.label_signal_noise:
-                label = np.zeros(len(events), dtype=bool)
-                label[:n_signal] = True
-            self.dvs_aedat4.appendEvents(events, signnoise_label=label)
-        if self.dvs_text is not None:
-            self.dvs_text.appendEvents(ev_dev, n_signal=sig)
-
-    def _sinks_open(self):
-        return self.dvs_h5 is not None or self.dvs_aedat2 is not None or self.dvs_aedat4 is not None or self.dvs_text is not None
-
-    def _write_held_runs(self):
-        """Finish and write, in order, every device-resident run still held for the open sinks (cleanup(), reset()).  Runs of
-        a failed instance cannot be written: they are dropped with an error in the log."""
-        q = self.__dict__.get("_sink_runs")
-        while q:
-            pend = q[0]
-            try:
-                pend.result()  # writes it and takes it off the queue
-            except Exception as e:
-                logger.error("v2e_amd.EventEmulator: %d enqueued run(s) not written to the event files: %s", len(q), e)
-                q.clear()
-            if q and q[0] is pend:  # (a result computed before it could be written)
-                q.pop(0)
-
-    def _write_run(self, pend, r, rows_dev, rows_host):
-        """_write_events for a whole device-resident run (emulator.py:953-977 per frame): the run's rows go to every open
-        sink, with the per-frame signal / noise labels of its records.  The rows are final on the device (result() waited for
-        them); the packing, formatting and copies run on the sinks' own streams."""
-        total = int(rows_dev.shape[0])
-        off = r["ev_offset"].astype(np.int64)
-        nsig = r["n_signal"].astype(np.int64)
-        nev = r["n_events"].astype(np.int64)
-        if self.dvs_h5 is not None:
-            if total > 0:
-                from .sinks import pack_h5
-                side = self.__dict__.get("_h5_stream") or torch.cuda.Stream(rows_dev.device)
-                self._h5_stream = side
-                with torch.cuda.stream(side):
-                    temp = pack_h5(rows_dev).cpu().numpy().view(np.uint32)
-                self.dvs_h5_dataset.resize(self.dvs_h5_dataset.shape[0] + temp.shape[0], axis=0)
-                self.dvs_h5_dataset[-temp.shape[0]:] = temp
-            if self.frame_ev_idx_dataset is not None:  # after each frame's events (emulator.py:979-983)
-                ends = self.dvs_h5_dataset.shape[0] - total + np.cumsum(nev)
-                self.frame_ev_idx_dataset[pend.frame0:pend.frame0 + len(ends)] = ends.astype(np.uint64)
-        if total == 0:
-            return
-        if self.dvs_aedat2 is not None:
-            self.dvs_aedat2.appendRun(rows_dev, off, nsig)
-        if self.dvs_aedat4 is not None:
-            if rows_host is None:
-                rows_host = rows_dev.cpu().numpy()
-            label = None
-            if self.label_signal_noise:
-                label = np.zeros(total, dtype=bool)
-                for o, k in zip(off, nsig):
-                    label[o:o + k] = True
-            self.dvs_aedat4.appendEvents(rows_host, signnoise_label=label)
-        if self.dvs_text is not None:
-            self.dvs_text.appendRun(rows_dev, off, nsig)
+        model_states.save_pixel_states(self)
 
     # ------------------------------------------------------------- centre-surround
-    MAX_CHANGE_TO_TERMINATE_EULER_SURROUND_STEPPING = 1e-5  # emulator.py:52
     CSDVS_RUN_MAX_STEPS = 8192  # Euler steps per frame a device-resident run enqueues up front
     CSDVS_RUN_MAX_TOTAL_STEPS = 65536  # ... and per run: every step is a launch (a graph node), taken or not (round-4 advisor)
 
@@ -1048,7 +745,7 @@ class EventEmulator(object):
         if use_graph is True:
             # the default: one hipGraph per run -- from the SECOND run of a length on.  Capturing and instantiating the graph costs ~2.3 ms,
             # more than it saves a run that is never repeated (an emulator per clip, BASELINE configs[2]: 88.3 -> 86.0 ms per clip)
-            seen = self.__dict__.setdefault("_blocking_lengths", {})
+            seen = self._blocking_lengths
             n = int(frames.shape[0])
             if seen.get(n, 0) == 0:
                 use_graph, pipelined = 0, False
@@ -1082,8 +779,7 @@ class EventEmulator(object):
         cleanup()).  Either makes the run a probed one: the per-frame kernels instead of k_chain, never pipelined, three small
         launches beside them (v2e_emu_set_probes).
         """
-        if getattr(self, "_failed", None):
-            raise _capi.V2EAmdError("a previous device-resident run failed (%s); call reset()" % self._failed)
+        self._raise_if_failed()
         if self.rng_mode != "philox":
             raise ValueError("generate_events_batch needs rng_mode='philox' (tape mode needs the host per frame)")
         if self.show_dvs_model_state is not None:
@@ -1117,8 +813,7 @@ class EventEmulator(object):
             start = 1
         nrun = F - start
         if nrun <= 0:
-            empty = torch.empty((0, 4), dtype=torch.float32, device=eng.device)
-            pend = _PendingRun(self, None, None, None, counts, start, return_device, empty)
+            pend = runs.PendingRun(self, counts, start, return_device, empty=torch.empty((0, 4), dtype=torch.float32, device=eng.device))
             if probe_pixels is not None:
                 pend.probes = {k: np.empty((0, len(user_idx))) for k in PIXEL_STATE_SERIES}
             return pend
@@ -1130,25 +825,8 @@ class EventEmulator(object):
                     t_frames[f], tp))
             t_prev.append(tp)
             tp = t_frames[f]
-        if self.photoreceptor_noise:  # emulator.py:694-703, the noise plane stays on the device for the whole run
-            if self.photoreceptor_noise_arr is None:
-                self._pn_plane = torch.zeros((1, eng.npx_pad), dtype=torch.float64, device=eng.device)
-                self.photoreceptor_noise_arr = eng.plane(self._pn_plane)
-            rates = [1.0 / (t_frames[f] - t_prev[f - start]) for f in range(start, F)]
-            if self.photoreceptor_noise_vrms is not None:
-                self._pn_vrms = float(self.photoreceptor_noise_vrms)
-            else:
-                # the reference recomputes the amplitude when the sample rate has moved by 10 % from the rate it was last
-                # computed for (emulator_utils.py:217-220); inside one device-resident run the amplitude is one number, so
-                # every frame of the run must stay within 10 % of the rate that number belongs to
-                if self._pn_last_rate is None or abs(rates[0] / self._pn_last_rate - 1) >= 0.1:
-                    self._pn_vrms = photoreceptor_noise_vrms(self.shot_noise_rate_hz, self.cutoff_hz, rates[0],
-                                                             self.pos_thres_nominal, self.neg_thres_nominal, self.sigma_thres)
-                    self._pn_last_rate = rates[0]
-                if any(abs(r / self._pn_last_rate - 1) >= 0.1 for r in rates):
-                    raise ValueError("photoreceptor_noise: the frame interval moves by more than 10 % from the rate the noise "
-                                     "amplitude was computed for inside this run; split the run there (or use generate_events "
-                                     "per frame)")
+        if self.photoreceptor_noise:
+            self._prepare_pnoise(eng, [1.0 / (t_frames[f] - t_prev[f - start]) for f in range(start, F)])
             eng.set_pnoise(self._pn_plane, None)
         cs_steps_dev = None
         if self.csdvs_enabled:
@@ -1164,7 +842,6 @@ class EventEmulator(object):
                                  "enqueued up front (mostly no-op launches once the diffuser has settled); beyond %d split the run or use "
                                  "generate_events per frame" % (sum(q[0] for q in pars), nrun, self.CSDVS_RUN_MAX_TOTAL_STEPS))
             cs_steps_dev = torch.zeros(nrun, dtype=torch.int32, device=eng.device)
-            import ctypes as C
             ns = (C.c_int * nrun)(*[q[0] for q in pars])
             ap = (C.c_double * nrun)(*[q[1] for q in pars])
             ah = (C.c_double * nrun)(*[q[2] for q in pars])
@@ -1172,48 +849,17 @@ class EventEmulator(object):
             _capi.check(eng.lib.v2e_emu_set_csdvs_run(eng._h, scratch.data_ptr(), lp_new.data_ptr(), ap, ah, ns, nrun,
                                                       float(self.MAX_CHANGE_TO_TERMINATE_EULER_SURROUND_STEPPING),
                                                       cs_steps_dev.data_ptr()), "v2e_emu_set_csdvs_run")
-        rec_claim = 0
-        if self.record_single_pixel_states is not None:
-            # emulator.py:985-1009 frame by frame: a frame that finds the series full saves the file and ends the recording.  Samples
-            # of runs enqueued and not yet read count as taken
-            held = self.__dict__.get("_sink_runs") or ()
-            room = self.SINGLE_PIXEL_MAX_SAMPLES - self.single_pixel_sample_count - sum(p.probe_claim for p in held)
-            if room <= 0:
-                self._write_held_runs()
-                if self.record_single_pixel_states is not None:
-                    self.save_recorded_single_pixel_states()
-                    self.record_single_pixel_states = None
-            else:
-                rec_claim = min(nrun, room)
-        probe_idx = (probe_pixel_indices([self.record_single_pixel_states], H, W) if self.record_single_pixel_states is not None
-                     else []) + user_idx
+        rec_claim = runs.claim_samples(self, nrun) if self.record_single_pixel_states is not None else 0
+        recording = self.record_single_pixel_states is not None  # (a recorder whose series were full has ended in claim_samples)
+        probe_idx = (probe_pixel_indices([self.record_single_pixel_states], H, W) if recording else []) + user_idx
         P = self._params()
         if cap is None:
             cap = default_event_capacity(nrun, H, W)
-        # two buffer sets alternate between asynchronous runs; the synchronous call has a third of its own, so that a pending
-        # handle whose result() has not been read yet is never overwritten by it
-        which = 2 if _single_buffer else self.__dict__.setdefault("_async_flip", 0)
-        if not _single_buffer:
-            self._async_flip = which ^ 1
-        # the run that last used this buffer set and has not been read yet: collect it now -- its rows and records (and, for pipelined
-        # runs, its scratch set's pinned records) are about to be reused, and a later result() would hand back this run's data instead
-        slots = self.__dict__.setdefault("_async_slots", {})
-        old = slots.get(which)
-        old = old() if old is not None else None  # (weak: a handle the caller has dropped needs no collecting, and a strong reference
-        #                                            here would tie the emulator and its device memory into a cycle only the GC breaks)
-        if old is not None and old._res is None and old.recs is not None:
-            ev_old, counts_old = old.result()
-            if old.return_device and ev_old is not None:
-                old._res = (ev_old.clone(), counts_old)
-        held = self.__dict__.get("_sink_runs")
-        if held:  # a run held for the sinks (its handle dropped) in this buffer set: written, with every run before it, now
-            last = [p for p in held if p.which == which]
-            if last:
-                last[-1].result()
+        which = runs.take_buffer_set(self, _single_buffer)
         ev = eng.event_buffer(cap, which)
         recs = eng.alloc_recs(nrun, which)
         ug = int(use_graph)
-        if getattr(self, "_refr_mostly_on", False):
+        if self._refr_mostly_on:
             ug |= _capi.RUN_ONE_FRAME_PER_LAUNCH  # the speculating chain would redo most of its launches
         if (ug & (_capi.RUN_GRAPH | _capi.RUN_PROFILE)) == 0 and (pipelined or pipelined is None) and not _single_buffer:
             ug |= _capi.RUN_PIPELINED | (_capi.RUN_FRAMES_RESIDENT if frames_resident else 0)
@@ -1231,96 +877,17 @@ class EventEmulator(object):
             ticket = None
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(eng.device))
+        pend = runs.PendingRun(
+            self, counts, start, return_device, ev=ev, recs=recs, _done=done, ticket=ticket, which=which, frame0=self.frame_counter,
+            dts=np.asarray(t_frames[start:]) - np.asarray(t_prev), times=t_frames[start:], cs_steps_dev=cs_steps_dev,
+            probe_dev=probe_dev, probe_rec=recording, probe_claim=rec_claim,
+            # (the thresholds the reference would record where it holds Python floats, emulator.py:992-995: as they are now)
+            thres=(self.pos_thres if type(self.pos_thres) is float else None, self.neg_thres if type(self.neg_thres) is float else None))
         self.frame_counter += nrun
         self.t_previous = t_frames[-1]
-        dts = np.asarray(t_frames[start:]) - np.asarray(t_prev)
-        pend = _PendingRun(self, ev, recs, done, counts, start, return_device, None, dts, ticket)
-        pend.cs_steps_dev = cs_steps_dev
-        pend.which, pend.frame0 = which, self.frame_counter - nrun
-        pend.probe_dev, pend.probe_rec, pend.probe_claim = probe_dev, self.record_single_pixel_states is not None, rec_claim
-        pend.times = t_frames[start:]
-        # (the thresholds the reference would record where it holds Python floats, emulator.py:992-995: as they are now)
-        pend.thres = (self.pos_thres if type(self.pos_thres) is float else None, self.neg_thres if type(self.neg_thres) is float else None)
-        slots[which] = weakref.ref(pend)
-        if self._sinks_open() or pend.probe_rec:
+        self._async_slots[which] = weakref.ref(pend)
+        if event_files.any_open(self) or recording:
             # held strongly until its rows are in the files (its samples in single_pixel_states), in the order the runs were enqueued
             # (a handle the caller drops is written by the call that reuses its buffer set, or by cleanup())
-            self.__dict__.setdefault("_sink_runs", []).append(pend)
+            self._sink_runs.append(pend)
         return pend
-
-    def _finish_run(self, pend):
-        eng = self._engine
-        held = self.__dict__.get("_sink_runs")
-        if held and any(p is pend for p in held):
-            while held[0] is not pend:  # the files get the runs in the order they were enqueued
-                held[0].result()
-        if getattr(self, "_failed", None):  # an earlier pending run failed: the state this run started from is not the clip's
-            raise _capi.V2EAmdError("a previous device-resident run failed (%s); this run started from its state: call reset()"
-                                    % self._failed)
-        if pend.ticket is not None:
-            eng.run_wait(pend.ticket)  # (host-blocking; no device-side wait is put into any stream's queue)
-            r = eng.run_recs(pend.ticket)[:, 0]
-        else:
-            r = eng.read_recs_after(pend.recs, pend.done)[:, 0]
-        if self.refractory_period_s > 0:  # emulator.py:830 on the frames just run: how often was the rule active?
-            m = np.maximum(r["max_events"], 1)
-            self._refr_mostly_on = bool(np.mean(self.refractory_period_s > pend.dts / m) > 0.05)
-        # the device state has already advanced past the failed run: the instance refuses further frames until reset()
-        err = None
-        if (r["flags"] & _capi.FLAG_ITERS_CLAMPED).any():
-            err = ("a pixel produced more than max_iters=%d events in one frame; construct with a larger max_iters"
-                   % eng.max_iters)
-        elif (r["flags"] & _capi.FLAG_SYNC_TIMEOUT).any():
-            err = ("in-kernel workgroup rendezvous of a redo pass timed out (GPU shared with another process?); "
-                   "use_graph | 128 runs one frame per launch, which needs none")
-        elif (r["flags"] & _capi.FLAG_EVENTS_DROPPED).any():
-            err = "event buffer capacity %d exceeded (needed %d); pass a larger cap" % (
-                pend.ev.shape[1], int(r["n_events"].sum()))
-        if err is not None:
-            self._failed = err
-            raise _capi.V2EAmdError(err + " -- the pixel state is past this run: call reset() before feeding more frames")
-        pend.counts[pend.start:] = r["n_events"]
-        pend.rec_host = r
-        if getattr(pend, "cs_steps_dev", None) is not None:
-            self.cs_steps_taken.extend(int(v) for v in pend.cs_steps_dev.cpu().tolist())  # emulator.py:1124
-        total = int(r["n_events"].sum())
-        self.num_events_total += total
-        self.num_events_on += int(r["n_on"].sum())
-        self.num_events_off += int(r["n_off"].sum())
-        if pend.probe_dev is not None:
-            self._collect_probes(pend)
-        out = pend.ev[0, :total]
-        host = None if pend.return_device or total == 0 else out.cpu().numpy()
-        if held and held[0] is pend:
-            held.pop(0)
-            self._write_run(pend, r, out, host)
-        if pend.return_device:
-            return out, pend.counts
-        return host, pend.counts
-
-    def _collect_probes(self, pend):
-        """The block a probed run left on the device (v2e_emu_set_probes): the recorder's pixel, if it was on, is probe 0 and goes to
-        single_pixel_states as the per-frame path would have put it there (append_pixel_states); the caller's pixels to pend.probes."""
-        blk = self._engine.read_after(pend.probe_dev, pend.done)  # [F_run][probes][PROBE_FIELDS]
-        pend.probe_dev = None
-        times = np.asarray(pend.times, dtype=np.float64)
-        pos, neg = pend.thres
-        first = 0
-        if pend.probe_rec:
-            first = 1
-            if self.record_single_pixel_states is not None:
-                self.single_pixel_sample_count, stop = append_pixel_states(
-                    self.single_pixel_states, self.single_pixel_sample_count, self.SINGLE_PIXEL_MAX_SAMPLES, times, blk[:, 0, :], pos, neg)
-                if stop:  # emulator.py:1007-1009
-                    self.save_recorded_single_pixel_states()
-                    self.record_single_pixel_states = None
-        if blk.shape[1] > first:
-            user = blk[:, first:, :]
-            d = {"time": np.repeat(times[:, None], user.shape[1], axis=1)}
-            for i, name in enumerate(_capi.PROBE_FIELD_NAMES):
-                d[name] = np.ascontiguousarray(user[:, :, i])
-            if pos is not None:
-                d["pos_thres"][:] = pos
-            if neg is not None:
-                d["neg_thres"][:] = neg
-            pend.probes = d

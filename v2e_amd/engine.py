@@ -4,6 +4,10 @@ PyTorch is plumbing here: it owns the HBM allocations (state planes, frame and e
 buffers) and the HIP stream; all arithmetic happens in libv2e_amd.so.  `EmuEngine`
 advances `n_clips` independent pixel arrays in lock-step; the drop-in
 `EventEmulator` (v2e_amd/emulator.py) uses n_clips = 1.
+
+Holds: the pinned result arrays of the frame API (`_RowsPool`), and `EmuEngine` -- one method per C entry point, the device
+buffers a hipGraph bakes pointers of (event rows per buffer set, records, probe blocks; cached so the pointers stay), and the two
+side streams results are read on.  Every attribute of an engine is created in its constructor.
 """
 import ctypes as C
 import weakref
@@ -102,6 +106,7 @@ class EmuEngine:
     """Device state + kernels of `n_clips` DVS pixel arrays of size H x W."""
 
     def __init__(self, H, W, n_clips=1, device="cuda", max_iters=64):
+        self._h = None  # the C handle; declared before anything below can raise: __del__ closes a half-built engine too
         self.H, self.W, self.n_clips = int(H), int(W), int(n_clips)
         self.device = torch.device(device)
         if self.device.type != "cuda" or not torch.cuda.is_available():
@@ -120,14 +125,19 @@ class EmuEngine:
         self._h = h
         self.f64_state = None
         self.lp = self.base = self.ts_mem = self.pos_thres = self.neg_thres = self.noise_rate = None
-        self._events = None
-        self._events_tmp = None
+        self._events = None  # event rows [n_clips][cap][4] of buffer set 0 (the frame API's, too)
+        self._events_tmp = None  # ... and the tape path's second buffer of that shape (the shuffle gathers from one into the other)
+        self._events_sets = {}  # buffer set (1, 2) -> event rows
+        self._recs_cache = {}  # (frames, buffer set) -> device records
+        self._probe_cache = {}  # (frames, probes, buffer set) -> device probe block
+        self._recs_host = {}  # shape -> pinned staging of read_recs_after
+        self._side_streams = {}  # "copy" / "join" -> torch stream, made when first needed
         self._dev_index = self.device.index
         self._rows_pool = _RowsPool()  # pinned result arrays of the frame API
         self._rows_est = 0
 
     def close(self):
-        if getattr(self, "_h", None):
+        if self._h:
             self.lib.v2e_emu_destroy(self._h)
             self._h = None
 
@@ -239,7 +249,7 @@ class EmuEngine:
     def probe_buffer(self, n_frames, n_probes, which=0):
         """Device float64 [F][P][PROBE_FIELDS] for set_probes, cached per (F, P, set) like alloc_recs: the hipGraph of a probed run
         bakes the pointer in."""
-        cache = self.__dict__.setdefault("_probe_cache", {})
+        cache = self._probe_cache
         key = (n_frames, n_probes, which)
         if key not in cache:
             if len(cache) > 8:
@@ -249,13 +259,16 @@ class EmuEngine:
 
     def read_after(self, t, done_event):
         """A small device tensor as a numpy array, copied on the side stream of read_recs_after once `done_event` has completed."""
-        cs = self.__dict__.get("_copy_stream")
-        if cs is None:
-            cs = self._copy_stream = torch.cuda.Stream(self.device)
+        cs = self._side_stream("copy")
         with torch.cuda.stream(cs):
             if done_event is not None:
                 cs.wait_event(done_event)
             return t.cpu().numpy()
+
+    def _side_stream(self, name):
+        if name not in self._side_streams:
+            self._side_streams[name] = torch.cuda.Stream(self.device)
+        return self._side_streams[name]
 
     def shot(self, P, frame_dev, frame_idx, shot_rand):
         check(self.lib.v2e_emu_shot(self._h, C.byref(P), _ptr(frame_dev), _DT[frame_dev.dtype],
@@ -284,20 +297,15 @@ class EmuEngine:
     def event_buffer(self, cap, which=0):
         """Device [n_clips][cap][4] float32 buffer, grown geometrically (`which`: one of several sets, so that the events of
         a run can still be read while the next run writes another set; set 0 is also the frame-at-a-time API's)."""
-        if which:
-            sets = self.__dict__.setdefault("_events_sets", {})
-            cur = sets.get(which)
-            if cur is None or cur.shape[1] < cap:
-                ncap = max(int(cap), 1024) if cur is None else max(int(cap), 2 * cur.shape[1])
-                cur = sets[which] = torch.empty((self.n_clips, ncap, 4), dtype=torch.float32, device=self.device)
-            return cur
-        if self._events is None or self._events.shape[1] < cap:
-            ncap = max(int(cap), 1024)
-            if self._events is not None:
-                ncap = max(ncap, 2 * self._events.shape[1])
-            self._events = torch.empty((self.n_clips, ncap, 4), dtype=torch.float32, device=self.device)
-            self._events_tmp = None
-        return self._events
+        cur = self._events_sets.get(which) if which else self._events
+        if cur is None or cur.shape[1] < cap:
+            ncap = max(int(cap), 1024, 0 if cur is None else 2 * cur.shape[1])
+            cur = torch.empty((self.n_clips, ncap, 4), dtype=torch.float32, device=self.device)
+            if which:
+                self._events_sets[which] = cur
+            else:
+                self._events, self._events_tmp = cur, None
+        return cur
 
     def emit(self, P, frame_idx, events, ts_table=None, ev_offset0=None):
         n_ts = 0 if ts_table is None else int(ts_table.shape[-1])
@@ -368,9 +376,7 @@ class EmuEngine:
     def run_done_event(self):
         """A torch event behind every piece of every pipelined run (use_graph | RUN_PIPELINED) enqueued so far: recorded on a stream of the
         engine that waits for them (v2e_emu_run_join), never on the caller's stream -- which carries the next run's chain."""
-        js = self.__dict__.get("_join_stream")
-        if js is None:
-            js = self._join_stream = torch.cuda.Stream(self.device)
+        js = self._side_stream("join")
         e0 = torch.cuda.Event()  # what the caller's stream holds (the run's chain; the whole run where the library did not overlap it)
         e0.record(torch.cuda.current_stream(self.device))
         js.wait_event(e0)
@@ -437,7 +443,7 @@ class EmuEngine:
     def alloc_recs(self, n_frames, which=0):
         """Device record array [F][n_clips] (struct v2e_frame_rec = 32 bytes), cached per (F, set) so that
         the hipGraph of run() (which bakes the pointer in) stays valid across calls."""
-        cache = self.__dict__.setdefault("_recs_cache", {})
+        cache = self._recs_cache
         key = (n_frames, which)
         if key not in cache:
             if len(cache) > 8:
@@ -465,10 +471,8 @@ class EmuEngine:
     def read_recs_after(self, recs_dev, done_event):
         """Records of a run as a structured numpy array, copied on a side stream once `done_event` (recorded behind the run)
         has completed: later runs already enqueued on the main stream are not waited for."""
-        cs = self.__dict__.get("_copy_stream")
-        if cs is None:
-            cs = self._copy_stream = torch.cuda.Stream(self.device)
-        host = self.__dict__.setdefault("_recs_host", {})
+        cs = self._side_stream("copy")
+        host = self._recs_host
         key = tuple(recs_dev.shape)
         if key not in host:
             host[key] = torch.empty(recs_dev.shape, dtype=torch.uint8).pin_memory()
@@ -482,7 +486,5 @@ class EmuEngine:
 
     @staticmethod
     def recs_to_numpy(recs_dev):
-        dt = np.dtype([("max_events", "<i4"), ("flags", "<u4"), ("n_signal", "<u4"), ("n_events", "<u4"),
-                       ("n_on", "<u4"), ("n_off", "<u4"), ("ev_offset", "<u8")])
         a = recs_dev.cpu().numpy()
-        return a.view(dt).reshape(a.shape[0], a.shape[1])
+        return a.view(_REC_DT).reshape(a.shape[0], a.shape[1])
