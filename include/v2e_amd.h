@@ -640,6 +640,39 @@ int v2e_tensorize_voxel_finish(int64_t *acc, int64_t n, float *out, int clear, v
  * maximum after the last plane. */
 int v2e_tensorize_surface_finish(void *planes, int n_planes, int64_t plane_words, uint32_t *state, void *stream);
 
+/* Event counts of one clip for many thresholds in one pass (v2e_amd/csrc/sweep.hip; host side v2e_amd/sweep.py, ThresholdSweep).
+ * Replaces the reference's threshold searches, which run the whole clip through one emulator per threshold:
+ * dataset_scripts/ddd/ddd_find_thresholds.py:120-155 (reset, generate_events per frame, select_events_in_roi, count the polarities;
+ * 95 thresholds) and v2ecore/thres_estimator.py (all of v2e.py per threshold).
+ * Column j is the emulator EventEmulator(pos_thres = pos[j], neg_thres = neg[j], rng_mode = "philox", shot_noise_rate_hz = 0) with
+ * the model parameters of *p, fresh, given the F frames one by one (clip 0; the first frame initialises it and emits nothing; the
+ * state is float64 when cutoff_hz > 0, float32 otherwise).  counts_dev[j] = { ON, OFF } events with roi[0] <= x <= roi[1] and
+ * roi[2] <= y <= roi[3] (inclusive, v2e_utils.select_events_in_roi) -- exact while the refractory rule (emulator.py:830) never
+ * switches on in column j.  The kernel runs every column as if the rule were off; rule_on_dev[j] = 1 says that it would have
+ * switched on in some frame, and that the column's counts are to be recomputed with the emulator itself.
+ * frames: device uint8 [F][H][W] (frame_dtype must be V2E_DT_U8); t_frames: host, F strictly increasing times, t_frames[0] >= 0;
+ * pos, neg: host, T positive thresholds; counts_dev (uint64 [T][2]) and rule_on_dev (int32 [T]) are device buffers of the caller's,
+ * overwritten.  The library's only scratch of its own is the table of per-frame scalars and thresholds, uploaded from host memory
+ * by the call (which is therefore not for stream capture).  Everything is enqueued on `stream`.  V2E_EINVAL for another frame type, F < 2, T < 1, an empty or out-of-sensor ROI, times that do not increase, a
+ * threshold that is not positive. */
+typedef struct v2e_sweep_params {
+    double sigma_thres;
+    double cutoff_hz;
+    double leak_rate_hz;
+    double leak_jitter_fraction;
+    double noise_rate_cov_decades;
+    double refractory_period_s;
+    uint64_t seed;
+    int32_t cols_per_thread; /* columns a thread carries in registers: 0 (the library's default), 4, 8 or 16 */
+    int32_t reserved_;       /* 0 */
+} v2e_sweep_params;
+int v2e_thres_sweep(const void *frames, int frame_dtype, int F, int H, int W, const double *t_frames, const v2e_sweep_params *p,
+                    const double *pos, const double *neg, int T, const int roi[4], uint64_t *counts_dev, int32_t *rule_on_dev,
+                    void *stream);
+/* v2e_thres_sweep_info: the kernel a sweep with this state type / kind of thresholds / cols_per_thread runs: the columns per
+ * thread in force, its vector registers per lane, and how many of its 256-thread workgroups a CU holds.  Outputs may be null. */
+int v2e_thres_sweep_info(int f64_state, int scalar_thres, int cols_per_thread, int *cols_out, int *vgprs, int *workgroups_per_cu);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,21 @@ class ConvDesc(C.Structure):
     ]
 
 
+class SweepParams(C.Structure):
+    """struct v2e_sweep_params."""
+    _fields_ = [
+        ("sigma_thres", C.c_double),
+        ("cutoff_hz", C.c_double),
+        ("leak_rate_hz", C.c_double),
+        ("leak_jitter_fraction", C.c_double),
+        ("noise_rate_cov_decades", C.c_double),
+        ("refractory_period_s", C.c_double),
+        ("seed", C.c_uint64),
+        ("cols_per_thread", C.c_int32),
+        ("reserved_", C.c_int32),
+    ]
+
+
 _vp, _i, _u32, _u64, _i64, _d = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_int64, C.c_double
 _PP = C.POINTER(EmuParams)
 
@@ -172,6 +187,9 @@ SIGNATURES = {
     "v2e_tensorize_move_zero": (_i, [_vp, _i64, _vp, _i64, _vp]),
     "v2e_tensorize_voxel_finish": (_i, [_vp, _i64, _vp, _i, _vp]),
     "v2e_tensorize_surface_finish": (_i, [_vp, _i, _i64, _vp, _vp]),
+    "v2e_thres_sweep": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_d), C.POINTER(SweepParams), C.POINTER(_d), C.POINTER(_d), _i,
+                             C.POINTER(_i), _vp, _vp, _vp]),
+    "v2e_thres_sweep_info": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
 }
 
 # dev entry points the library exports outside include/v2e_amd.h: typed by lib() when present, never required
