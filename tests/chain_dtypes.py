@@ -92,13 +92,15 @@ def exact_multiple_clip(n, H, W, seed):
 def _exact_floor_and_rem(am, theta, R):
     """floor(am / theta) and am - floor * theta of operands held in type R, exactly.  fmod is exact in any format; in a format with
     p more mantissa bits than R's the multiple am - fmod is exact for quotients below 2^p, and so is its division by theta
-    (float32 operands in float64: p = 29; float64 operands in longdouble: p = 11 where longdouble is the x87 format)."""
+    (float32 operands in float64: p = 29; float64 operands in longdouble: p = 11 where longdouble is the x87 format).  Where theta
+    is a power of two the multiple is am with its low bits cleared and the division only moves the exponent: exact at any quotient."""
     W = np.float64 if np.dtype(R) == np.float32 else np.longdouble
     p = np.finfo(W).nmant - np.finfo(R).nmant
     a, t = np.asarray(am, R).astype(W), np.asarray(theta, R).astype(W)
     rem = np.fmod(a, t)
     q = np.rint((a - rem) / t)
-    assert p > 0 and (q.size == 0 or q.max() < 2.0 ** p), "quotient beyond what %s holds exactly" % np.dtype(W).name
+    pow2 = np.frexp(t)[0] == 0.5
+    assert p > 0 and np.all((q < 2.0 ** p) | pow2), "quotient beyond what %s holds exactly" % np.dtype(W).name
     return q.astype(np.int64), rem
 
 
@@ -124,10 +126,13 @@ def remainder_zero(am, theta, R):
     return (rem == 0) & (q > 0)
 
 
-def frame_quotients(ora_before_base, ora_after_lp, pos_thres, neg_thres, R):
-    """(am, theta, is_pos) of a frame from the oracle's planes around it (leak off): am = |lp_new - base| as the kernel computes it in
-    type R, theta the divisor of its sign."""
-    diff = (np.asarray(ora_after_lp, R) - np.asarray(ora_before_base, R)).astype(R)
+def frame_quotients(ora_before_base, ora_after_lp, pos_thres, neg_thres, R, leak=None):
+    """(am, theta, is_pos) of a frame from the oracle's planes around it: am = |lp_new - base| as the kernel computes it in type R,
+    theta the divisor of its sign.  leak: the frame's leak step (float32, per pixel), taken off the base first; None: leak off."""
+    base = np.asarray(ora_before_base, R)
+    if leak is not None:
+        base = (base - np.asarray(leak, np.float32).astype(R)).astype(R)
+    diff = (np.asarray(ora_after_lp, R) - base).astype(R)
     is_pos = diff > 0
     theta = np.where(is_pos, np.asarray(pos_thres, R), np.asarray(neg_thres, R)).astype(R)
     return np.abs(diff), theta, is_pos

@@ -173,3 +173,171 @@ def test_refractory_clip_has_columns_on_both_sides_of_the_rule():
     # (at 0.13 the rule filters events: 4838 / 4838 with it, 4888 / 4885 without; at 0.15 it is on for a frame and filters nothing)
     assert (ref["on"][0], ref["off"][0]) == (4838, 4838) and (plain["on"][0], plain["off"][0]) == (4888, 4885)
     assert all((ref["on"][j], ref["off"][j]) == (plain["on"][j], plain["off"][j]) for j in range(2, 11))
+
+
+# ------------------------------------------------------------------------------------------------ the aimed inputs, by the oracle alone
+import chain_dtypes as cd  # noqa: E402
+
+
+def _aimed_stats(instantiation):
+    """Over all columns and frames of aimed_clip, from the oracle's planes around each frame (one oracle run per column): the
+    pixel-frame-columns whose reciprocal estimate is one too large, one too small, one too small on an exact multiple (r0 == bt),
+    and the ON / OFF split of all of them."""
+    from oracle import oracle as orc
+    inst = tsr.INSTANTIATIONS[instantiation]
+    R = inst["state"]
+    frames, times, thetas = tsr.aimed_clip(instantiation)
+    tot = dict(n=0, fires=0, large=0, small=0, small_exact=0, on=0, off=0)
+    for th in thetas:
+        def watch(k, before, ora):
+            # the divisors as the instantiation holds them: the Python double (in float32 state: rounded to it), or the float32 plane
+            pt, nt = (th, th) if inst["scalar"] else (ora.pos_thres_arr, ora.neg_thres_arr)
+            leak = tsr.aimed_leak(inst["model"], times, k, np.broadcast_to(np.float32(pt), before.shape))
+            am, t, pos = cd.frame_quotients(before, ora.lp_log_frame, pt, nt, R, leak=leak)
+            off = cd.estimate_off_by_one(am, t, R)
+            zero = cd.remainder_zero(am, t, R)
+            # the predicate's floor is the oracle's count
+            assert np.array_equal(cd.estimate(am, t, R) - off, np.where(pos, ora.last["pos_cnt"], ora.last["neg_cnt"]))
+            tot["n"] += am.size
+            tot["fires"] += int((am >= t).sum())
+            tot["large"] += int((off == 1).sum())
+            tot["small"] += int((off == -1).sum())
+            tot["small_exact"] += int(((off == -1) & zero).sum())
+            tot["on"] += int(((off != 0) & pos).sum())
+            tot["off"] += int(((off != 0) & ~pos).sum())
+
+        kw = dict(pos_thres=th, neg_thres=th, shot_noise_rate_hz=0.0, refractory_period_s=0.0, **inst["model"])
+        out = cd.oracle_run(orc, kw, frames, list(times), seed=tsr.SEED, watch=watch)
+        assert out["state"] == R
+        if not inst["scalar"]:  # sigma_thres selects the per-pixel kernel and leaves every threshold at the aimed value
+            pt = orc.OracleEmulator(seed=tsr.SEED, rng_mode="philox", **kw)
+            pt.generate_events(frames[0], float(times[0]))
+            assert np.all(pt.pos_thres_arr == np.float32(th)) and np.all(pt.neg_thres_arr == np.float32(th))
+    return tot
+
+
+# measured at 33 x 37, 8 frames, 12 columns = 102 564 pixel-frame-columns per instantiation (asked of each: at least 20):
+#                 fire     too large   too small   too small, r0 == bt   ON / OFF of those
+#   f32_scalar    69 433   2 745       13 591      13 591                8 716 / 7 620
+#   f32_pixel     69 433   2 745       13 591      13 591                8 716 / 7 620
+#   f64_scalar    75 783   1 436       19 300      19 300                10 888 / 9 848
+#   f64_pixel     82 670   258         13 224      13 224                6 133 / 7 349      (with AIM_LEAK; 0 too large without)
+AIMED_FLOOR = 20
+
+
+@pytest.mark.parametrize("instantiation", sorted(tsr.INSTANTIATIONS))
+def test_aimed_clip_reaches_both_fixup_arms(instantiation):
+    """The table above.  Every estimate that is too small sits on an exact multiple: theta = d / n was chosen so.
+
+    k_sweep<double, *, false> (float32 thresholds, float64 state) needs a device of its own for `mag -= r0 < 0`: the estimate
+    fl(am * fl(1 / theta)) is one too large only if am lies below a multiple m theta by less than about m theta 2^-52.  Without a
+    leak am is a sum of float32 values (lin-log levels and steps fl32(count * theta), all of magnitude 0.05 .. 5.6) and m theta a
+    small multiple of a float32 value, so both are multiples of 2^-28 and differ by 0 or by at least 2^-28 > 5.6 * 2^-52: the arm
+    cannot be reached (measured: 0).  AIM_LEAK moves the base by about one unit in its last place per frame, which is that close;
+    the predicate then takes the frame's leak step off the base, and its floor still is the oracle's count."""
+    inst = tsr.INSTANTIATIONS[instantiation]
+    frames, times, thetas = tsr.aimed_clip(instantiation)
+    assert frames.shape == (tsr.AIM_FRAMES, 37, 33) and frames.dtype == np.uint8 and len(thetas) <= 12 and times[0] > 0
+    assert len(set(thetas)) == len(thetas) and min(thetas) >= 0.05 and max(thetas) <= 1.0
+    assert (inst["model"]["cutoff_hz"] > 0) == (inst["state"] == np.float64) and (inst["model"]["sigma_thres"] > 0) == (not inst["scalar"])
+    if inst["state"] == np.float64:  # eps clamps at every level, in every frame
+        assert tsr.clamp_eps(np.zeros((len(times), 1, 1), np.uint8), times, inst["model"]["cutoff_hz"]).min() > 2.0
+    tot = _aimed_stats(instantiation)
+    print(instantiation, tot)
+    assert tot["small"] >= AIMED_FLOOR and tot["small_exact"] >= AIMED_FLOOR
+    assert tot["on"] >= AIMED_FLOOR and tot["off"] >= AIMED_FLOOR
+    assert tot["large"] >= AIMED_FLOOR
+    ref = tsr.aimed_reference(instantiation)
+    assert np.all(ref["on"] > 0) and np.all(ref["off"] > 0) and not ref["rule_on"].any()
+    assert len({(int(a), int(b)) for a, b in zip(ref["on"], ref["off"])}) == len(thetas)
+
+
+def test_column_model_is_the_oracle_where_both_can_run():
+    """column_model (float32 state) on the existing clip's scalar_f32 configuration, all 11 columns, and on the scalar float32
+    aimed clip; its float64 form on the scalar float64 aimed clip (eps clamped: lp == L).  It may then stand in for the oracle."""
+    frames, times = tsr.clip()
+    ref = tsr.reference("scalar_f32")
+    got = tsr.model_sweep(frames, times, tsr.THRESHOLDS, tsr.THRESHOLDS, tsr.ROI)
+    assert np.array_equal(got["on"], ref["on"]) and np.array_equal(got["off"], ref["off"])
+    for instantiation, R in (("f32_scalar", np.float32), ("f64_scalar", np.float64)):
+        frames, times, thetas = tsr.aimed_clip(instantiation)
+        ref = tsr.aimed_reference(instantiation)
+        got = tsr.model_sweep(frames, times, thetas, thetas, tsr.WHOLE, R)
+        assert np.array_equal(got["on"], ref["on"]) and np.array_equal(got["off"], ref["off"])
+
+
+def test_generic_division_and_wave_sum_inputs():
+    """One pixel's per-frame count on the alternating clip is beyond QMAX of its state type (5 810 436 > 1e6 at 2^-20 in float32
+    state, 1 487 471 616 > 1e9 at 2^-28 in float64 state) and fits an int; the 8 x 8 sensor passes 2^32 ON events at 24 frames
+    (4 462 414 848 ON, 4 090 546 944 OFF) while a pixel's own total is 69 725 232."""
+    for name, qmax in (("f32", 1e6), ("f64", 1e9)):
+        R, theta, model = tsr.GENERIC[name]
+        frames, times = tsr.alternating_clip(37, 33, 3)
+        on, off = tsr.column_model(frames, times, theta, theta, ((16, 16), (9, 9)), R)
+        print(name, on, off)
+        assert qmax < on < 2 ** 31 and qmax < off < 2 ** 31
+        assert (model["cutoff_hz"] > 0) == (R == np.float64)
+        if R == np.float64:
+            assert tsr.clamp_eps(frames * 0, times, model["cutoff_hz"]).min() > 2.0
+    n, (on, off), one = tsr.wave_sum_frames()
+    print(n, on, off, one)
+    assert n <= 40 and max(on, off) > 2 ** 32 and one < 2 ** 32
+    assert (on % 2 ** 32, off % 2 ** 32) != (on, off)  # a 32-bit wave sum gives another number
+
+
+def test_levels_clip_holds_every_grey_level_and_starts_late():
+    frames, times = tsr.levels_clip()
+    late, early = tsr.levels_clip(), tsr.levels_clip(0.0)
+    assert times[0] > 0 and early[1][0] == 0 and np.array_equal(late[0], early[0])
+    assert np.allclose(np.diff(late[1]), np.diff(early[1]), rtol=0, atol=1e-15)
+    d = np.diff(times)
+    assert d.min() >= 0.0004 and d.max() <= 0.006 and len(set(np.round(d, 9))) == len(d)
+    for f in frames:
+        assert len(np.unique(f)) == 256
+    steps = {(int(a), int(b)) for k in range(len(frames) - 1) for a, b in zip(frames[k].ravel()[:8], frames[k + 1].ravel()[:8])}
+    assert {(0, 20), (20, 21), (21, 255), (255, 21), (21, 20), (20, 0), (0, 255), (255, 20), (0, 21), (255, 0)} <= steps
+    # frame 0's eps is neither 0 nor clamped on some pixels (cutoff 100 Hz): (1 - eps) L + eps L is a rounded expression
+    e0 = tsr.clamp_eps(frames, times)[0]
+    assert ((e0 > 0) & (e0 < 1)).sum() > 100
+    # the start time is visible in the counts: a sweep that took frame 1's interval from t[0] would give the other reference
+    for name in ("defaults", "cutoff_f64"):
+        a, b = tsr.levels_reference(name), tsr.levels_reference(name, 0.0)
+        print(name, (a["on"] - b["on"]).tolist(), (a["off"] - b["off"]).tolist())
+        assert not (np.array_equal(a["on"], b["on"]) and np.array_equal(a["off"], b["off"]))
+        assert np.all(a["on"] > 0) and np.all(a["off"] > 0) and not a["rule_on"].any()
+
+
+def test_clamp_clip_has_eps_on_both_sides_of_one_in_every_frame():
+    frames, times = tsr.clamp_clip()
+    eps = tsr.clamp_eps(frames, times)
+    print([(int((e > 1).sum()), int((e < 1).sum())) for e in eps])
+    for e in eps[1:]:
+        assert (e > 1).sum() >= 100 and (e < 1).sum() >= 100
+    for leak in (True, False):
+        ref = tsr.clamp_reference(leak)
+        assert np.all(ref["on"] > 0) and np.all(ref["off"] > 0)
+    assert not np.array_equal(tsr.clamp_reference(True)["on"], tsr.clamp_reference(False)["on"])
+
+
+def test_threshold_clamp_case_clamps_a_share_of_the_pixels():
+    pos, neg = tsr.thres_clamp_fraction()
+    print(pos, neg)  # 0.344, 0.399
+    assert 0.1 <= pos <= 0.9 and 0.1 <= neg <= 0.9
+    ref = tsr.thres_clamp_reference()
+    assert np.all(ref["on"] > 0) and np.all(ref["off"] > 0) and not ref["rule_on"].any()
+    assert tsr.THRES_CLAMP["model"]["refractory_period_s"] == 0
+
+
+def test_lone_pixel_outside_the_roi_switches_the_rule_on():
+    (x0, x1), (y0, y1) = tsr.ROI
+    x, y = tsr.LONE_PIXEL
+    assert not (x0 <= x <= x1 and y0 <= y <= y1)
+    with_lone, without = tsr.lone_pixel_clip(True)[0], tsr.lone_pixel_clip(False)[0]
+    assert (with_lone != without).any(axis=0).sum() == 1 and (with_lone != without)[:, y, x].any()
+    ref, plain = tsr.lone_pixel_reference(True), tsr.lone_pixel_reference(False)
+    print(ref["rule_on"].tolist(), ref["max_m"].tolist(), plain["max_m"].tolist())
+    assert ref["rule_on"].tolist() == [True, True] + [False] * 9
+    # refr_on_n = 3 (REFRACTORY_S, 1 ms frames): without the lone pixel no pixel of the sensor, inside the ROI or not, gets there
+    assert not plain["rule_on"].any() and plain["max_m"].max() < 3 and ref["max_m"][:2].min() >= 3
+    assert ref["max_m_roi"].max() < 3 and ref["max_m"].max() <= 32
+    assert ref["on"][:5].min() > 0

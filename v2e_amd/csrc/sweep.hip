@@ -6,6 +6,7 @@
 // lp_log_frame once, draws the frame's leak jitter once, and carries TB columns of (base_log_frame, ON count, OFF count) in
 // registers; blockIdx.y is the chunk of TB columns.  Nothing is written per event, per frame or per pixel: the counts of the
 // pixels inside the ROI are summed per wave and workgroup and added to counts[T][2] with integer atomics (two runs are bit-equal).
+// A pixel's own ON (OFF) total of a column is a 32-bit register; every sum of pixels is 64-bit.
 //
 // Per frame and column the arithmetic is k_count's and k_emit's (emu_kernels.h), value for value: the leak step
 // ((float)dt * rate) * thp, base - leak, diff = lp - base, the floor division (k_chain's guarded reciprocal form, emu_chain.h: the
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(BLOCK) void k_sweep(SweepArgs a)
     static_assert(TB >= 1 && TB <= 32, "one flag bit per column of the chunk");
     __shared__ float s_lutL[256];
     __shared__ double s_lutI[256];
-    __shared__ uint32_t s_sum[BLOCK / WAVE][TB][2];
+    __shared__ unsigned long long s_sum[BLOCK / WAVE][TB][2];
     __shared__ uint32_t s_flag[BLOCK / WAVE];
     const int tid = threadIdx.x;
     // lin_log(x) and (x + 20) / 275 of the 256 grey levels, by the functions k_lut and the per-pixel path use
@@ -184,11 +185,13 @@ __global__ __launch_bounds__(BLOCK) void k_sweep(SweepArgs a)
     }
     if (!valid) flags = 0u;
 
-    // ---- wave sums, workgroup sums, one integer atomic per column and polarity
+    // ---- wave sums, workgroup sums, one integer atomic per column and polarity.  64 lanes of 32-bit counts sum to up to 38 bits:
+    // the 16-bit halves are summed apart (each sum stays below 2^22) and put together in 64 bits.
     const int lane = tid & (WAVE - 1), wid = tid / WAVE;
 #pragma unroll
     for (int c = 0; c < TB; ++c) {
-        const uint32_t so = wave_sum_u32(n_on[c]), sf = wave_sum_u32(n_off[c]);
+        const unsigned long long so = (unsigned long long)wave_sum_u32(n_on[c] & 0xFFFFu) + ((unsigned long long)wave_sum_u32(n_on[c] >> 16) << 16);
+        const unsigned long long sf = (unsigned long long)wave_sum_u32(n_off[c] & 0xFFFFu) + ((unsigned long long)wave_sum_u32(n_off[c] >> 16) << 16);
         if (lane == 0) { s_sum[wid][c][0] = so; s_sum[wid][c][1] = sf; }
     }
     const uint32_t wf = wave_or_u32(flags);

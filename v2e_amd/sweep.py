@@ -16,7 +16,8 @@ x0 <= x <= x1 and y0 <= y <= y1 that
 emits when the F frames are given to it one by one from a fresh instance (the first frame initialises it and emits nothing).
 Integers, no tolerance.  The refractory rule (emulator.py:830) couples the pixels of a frame; the kernel runs every column as if
 it were off and flags the columns in which it would have switched on, and those are recomputed here with the emulator itself
-(`SweepResult.rule_on` says which).
+(`SweepResult.rule_on` says which).  The sums over pixels are 64-bit; the one limit is a single pixel's own ON (or OFF) total of
+a column over the whole clip, which the kernel keeps in 32 bits: beyond 2^32 - 1 events of one polarity on one pixel it wraps.
 
 Out of scope: shot noise (it resets base_log_frame per column and adds rows), hdr, float frames, photoreceptor_noise, SCIDVS,
 CSDVS, tape mode, a clip streamed across several `run` calls, per-frame or per-pixel count maps, reading recordings.
