@@ -673,6 +673,37 @@ int v2e_thres_sweep(const void *frames, int frame_dtype, int F, int H, int W, co
  * thread in force, its vector registers per lane, and how many of its 256-thread workgroups a CU holds.  Outputs may be null. */
 int v2e_thres_sweep_info(int f64_state, int scalar_thres, int cols_per_thread, int *cols_out, int *vgprs, int *workgroups_per_cu);
 
+/* The spatio-temporal correlation filter (STCF; with one supporting neighbour jAER's BackgroundActivityFilter) scored for every
+ * (k, tau) in one pass over the rows of a device-resident run (v2e_amd/csrc/denoise.hip; host side v2e_amd/denoise.py,
+ * DenoiseSweep).  Rows are events[n][4] = (t, x = column, y = row, p), processed in row order; p is not read.  A row is bad if t is
+ * not finite or x / y is not an integer value inside [0,W) / [0,H): it reads and writes nothing, enters no histogram, is counted
+ * and gets keep = 0.  For a valid row i at pixel (x, y), each of the 8 neighbours q inside the sensor (centre excluded) gives
+ * age_q = (double)t_i - (double)T_q, T_q the t of the latest row j < i at q in this pass, else the carried last_t[q] (float32
+ * [H][W], -inf where no row has been yet); a neighbour outside the sensor or T_q = -inf gives +inf, a T_q later than t_i a negative
+ * age, kept as it is.  With a_1 <= ... <= a_8 the sorted ages, the row passes STCF(k, tau) iff a_k <= tau; after its ages are read
+ * the row sets last_t[x,y] = t_i whatever the filters say.  taus: device float64 [n_taus], 1 <= n_taus <= 256, finite, >= 0,
+ * strictly ascending (the caller checks); bin(a) = the number of taus strictly below a (bin n_taus: passes none), and
+ * hist[k-1][label][bin(a_k)] += 1 for k = 1 .. 8, hist a device uint64 [8][2][n_taus+1], label 1 = signal, 0 = noise.  All sums are
+ * integer atomics: the result depends on the row order only, not on scheduling, and a clip cut into passes gives the same sums.
+ * One pass (n <= 2^31 - 1 rows, H * W <= 2^31 - 1) is four calls with a sort of the keys between the first and the second:
+ * v2e_denoise_keys: keys[i] = pixel << 32 | i, or 0x7fffffffffffffff for a bad row (sorts last as int64); keep (uint8 [n] or null)
+ * gets 0 at bad rows.
+ * v2e_denoise_segments: sorted_keys = keys in ascending order; seg (int32 [H*W+1]): pixel p's rows are sorted_keys[seg[p] ..
+ * seg[p+1]), seg[H*W] = the number of valid rows; counters (device uint64 [2] or null): [0] += valid rows, [1] += bad rows.
+ * v2e_denoise_ages: ages, histogram and, with keep != null, keep[i] = (a_keep_k <= keep_tau) for every valid row.  The label of row
+ * i is labels[i] != 0 (uint8 [n]), or, with label_bounds (ascending int64 row indices of the whole call, this pass's row 0 having
+ * index row0: frame f's signal rows start at label_bounds[2f], its noise rows at label_bounds[2f+1]), signal iff an odd number
+ * of entries is <= row0 + i; with neither every row is signal.  last_t is only read.
+ * v2e_denoise_map_update: last_t[p] = the t of pixel p's last row of the pass; behind v2e_denoise_ages on the same stream.
+ * events must be 16-byte aligned. */
+int v2e_denoise_keys(const float *events, int64_t n, int H, int W, int64_t *keys, uint8_t *keep, void *stream);
+int v2e_denoise_segments(const int64_t *sorted_keys, int64_t n, int H, int W, int32_t *seg, uint64_t *counters, void *stream);
+int v2e_denoise_ages(const float *events, int64_t n, int H, int W, const int64_t *sorted_keys, const int32_t *seg, const float *last_t,
+                     const double *taus, int n_taus, const uint8_t *labels, const int64_t *label_bounds, int n_label_bounds,
+                     int64_t row0, uint64_t *hist, uint8_t *keep, int keep_k, double keep_tau, void *stream);
+int v2e_denoise_map_update(const float *events, const int64_t *sorted_keys, const int32_t *seg, int H, int W, float *last_t,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

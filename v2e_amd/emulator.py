@@ -239,6 +239,7 @@ class EventEmulator(object):
         self.single_pixel_states = None if self.record_single_pixel_states is None else {
             k: np.full(self.SINGLE_PIXEL_MAX_SAMPLES, np.nan) for k in PIXEL_STATE_SERIES}
         self.last_probes = None  # generate_events_batch(probe_pixels=...): the series of the last such call
+        self.last_n_signal = None  # the last finished device-resident run's signal rows per frame (PendingRun.n_signal, runs.py)
 
         # device-resident runs (runs.py); what is per clip is in reset()
         self._async_flip = 0  # the buffer set (0 / 1) the next asynchronous run writes

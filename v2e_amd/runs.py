@@ -54,6 +54,8 @@ class PendingRun:
     thres: tuple = (None, None)  # (pos, neg) as Python floats where the reference would record those (emulator.py:992-995)
     probes: dict = None    # probe_pixels=...: the ten series of the probed pixels, float64 [F_run, P] each (after result())
     rec_host: object = None  # the run's records as a structured host array [F_run] (after result())
+    n_signal: np.ndarray = None  # int64 [F], aligned with counts: each frame's rows start with that many signal rows, the rest
+    #                              are shot noise (0 for the clip's very first frame); after result()
     _res: tuple = None     # what result() returned
 
     @property
@@ -66,6 +68,7 @@ class PendingRun:
     def result(self):
         if self._res is None:
             if self.recs is None:
+                self.n_signal = self.emu.last_n_signal = np.zeros(len(self.counts), dtype=np.int64)
                 self._res = ((self.empty if self.return_device else None), self.counts)
             else:
                 self._res = finish(self)
@@ -152,6 +155,9 @@ def finish(pend):
         raise _capi.V2EAmdError(err + " -- the pixel state is past this run: call reset() before feeding more frames")
     pend.counts[pend.start:] = r["n_events"]
     pend.rec_host = r
+    pend.n_signal = np.zeros(len(pend.counts), dtype=np.int64)
+    pend.n_signal[pend.start:] = r["n_signal"]
+    emu.last_n_signal = pend.n_signal
     if pend.cs_steps_dev is not None:
         emu.cs_steps_taken.extend(int(v) for v in pend.cs_steps_dev.cpu().tolist())  # emulator.py:1124
     total = int(r["n_events"].sum())
