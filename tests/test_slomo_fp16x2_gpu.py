@@ -1,8 +1,7 @@
 """The default SuperSloMo convolution math (conv_math "auto" / "fp16x2": two float16 pieces per operand, v2e_amd/csrc/slomo_s3.h
 with NP = 2) pinned layer by layer and range slot by range slot.
 
-Layers: every k_conv_s3<..., 2> instantiation that the `np == 2` branch of conv_dispatch_s3 (v2e_amd/csrc/slomo.hip) can select
-by default, through the public v2e_conv2d_lrelu with split_kind = 2 | (scale_log2 << 8), against the float64-accumulating CPU
+Layers: every k_conv_s3<..., 2> instantiation that conv_dispatch_h2 (v2e_amd/csrc/slomo.hip) can select, through the public v2e_conv2d_lrelu with split_kind = 2 | (scale_log2 << 8), against the float64-accumulating CPU
 oracle at the project's bar (test_slomo_gpu.TOL), inside guard bands, and sample by sample.  A whole UNet pass cannot reach
 several of them (its 32-channel layers sit at full resolution, h % 32 == 0 and w % 32 == 0).
 
@@ -92,8 +91,8 @@ class _Layer:
         return y.cpu().numpy()
 
 
-# (k, cin0, cin1, cout, n, h, w): every `return launch_conv_s3<KS, CT, PT, WP, TW, NB, MODE, RG, 2>` of the np == 2 branch that the
-# default V2E_AMD_S3_VARIANT takes.  A tile is WP * PT * 32 / TW rows of TW pixels; "ragged" = the last tile row partly masked.
+# (k, cin0, cin1, cout, n, h, w): every `return launch_conv_s3<KS, CT, PT, WP, TW, NB, MODE, RG, 2>` of conv_dispatch_h2, the two-piece
+# tile selection.  A tile is WP * PT * 32 / TW rows of TW pixels; "ragged" = the last tile row partly masked.
 H2_CASES = [
     # 3x3, cout % 64 == 0: 64 x 64 register tiles, one kernel row of weights resident (RG)
     (3, 32, 0, 64, 2, 20, 32),      # <3,2,2,4,32,1,0,1,2>: 8 x 32 tiles, ragged (20 = 2 * 8 + 4)
@@ -245,6 +244,27 @@ def _check_pass(unet, x, tag):
         staged = float(np.array([m], np.uint32).view(np.float32)[0]) * 2.0 ** k
         assert 2.0 ** 13 <= staged < 2.0 ** 14, "%s: convolution %d would stage its largest input at %g" % (tag, i, staged)
     return am
+
+
+def test_a_pass_leaves_nothing_behind_for_a_stand_alone_layer():
+    """What a forward pass hands its layers (range slots, a pooled-copy request) ends with the pass: the same stand-alone
+    convolution before and after a tracked pass in the same process gives the same bits inside intact guard bands (with a
+    slot left over it would scale its operands and write the slot), and it leaves the pass's 32 slot words as they were."""
+    from v2e_amd.slomo import HipUNet
+    from v2e_amd.synth import portable_unet_state_dict
+    x0, x1, wt, b = _case_tensors((3, 16, 0, 64, 1, 16, 32))
+    layer = _Layer(wt, b)
+    before = layer.run(x0, x1, "fp16x2")
+    dev = torch.device("cuda")
+    sd = {k: torch.from_numpy(v) for k, v in portable_unet_state_dict(12, 5, 512).items()}
+    unet = HipUNet(sd, 12, 5, dev, "fp16x2")
+    x = (torch.rand((1, 12, 32, 32), generator=torch.Generator().manual_seed(1232)) - 0.4).to(dev)
+    y = unet.forward(x)
+    assert unet.fallbacks == 0 and bool(torch.isfinite(y).all())
+    am = _check_pass(unet, x, "fp16x2 1x32x32 cin 12")     # the pass was tracked: its slots hold its maxima
+    after = layer.run(x0, x1, "fp16x2")                     # guard bands are checked inside
+    assert np.array_equal(before, after), "a stand-alone layer changed after a forward pass in the same process"
+    assert np.array_equal(unet.range_slots(1, 32, 32), am), "a stand-alone layer wrote a range slot of the pass before it"
 
 
 SLOT_SHAPES = [(2, 64, 96), (3, 256, 320), (2, 32, 160), (1, 96, 64)]   # (n, h, w)

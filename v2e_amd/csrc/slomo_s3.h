@@ -453,15 +453,15 @@ void k_conv_s3(ConvArgs a)
 }
 
 template <int KS, int CT, int PT, int WP, int TW, int NB = 1, int MODE = 0, int RG = 0, int NP = 3>
-static int launch_conv_s3(const ConvArgs &a0, hipStream_t s)
+static int launch_conv_s3(const ConvArgs &a0, hipStream_t s, LayerCtx &ctx)
 {
     ConvArgs a = a0;
     constexpr int TH = WP * PT * 32 / TW;
     constexpr int PP = (TH + KS - 1) * (TW + KS - 1);
     constexpr int G = (KS == 3 && !RG) ? 9 : KS;
     constexpr size_t lds = (size_t)(2 * NP * PP + G * 2 * NP * CT * 32) * 16;
-    a.ypool = nullptr;
-    if (TW == 32 && PT == 2 && g_pool_out && a.h % 2 == 0 && a.w_ % 2 == 0) { a.ypool = g_pool_out; g_pool_out = nullptr; } // taken
+    ctx.pooled = TW == 32 && PT == 2 && ctx.pool_out && a.h % 2 == 0 && a.w_ % 2 == 0; // the tile that can write the pooled copy
+    a.ypool = ctx.pooled ? ctx.pool_out : nullptr;
     static_assert(lds <= 160 * 1024, "LDS");
     static bool attr_set = false; // one per instantiation
     if (!attr_set) {
