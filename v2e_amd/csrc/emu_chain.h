@@ -48,6 +48,11 @@ constexpr int CHAIN_K_MAX = 64; // (a lane per frame of a launch: rule threshold
 constexpr int CFRAME_THREADS = 1024;
 constexpr int CHAIN_SUB = 8; // frames of a sub-pass: their records are loaded together and decoded into registers at its start
 constexpr int CHAIN_MAX_ITERS = 1024; // k_cframe keeps one total per key in LDS
+// !FUSED: a launch's frames take very few distinct dt_over_tau bit patterns (times i / fps: two, now and then three), so what a record
+// decodes to beside its random part -- (1 - eps, eps * L), a function of the pixel byte and the frame's dt_over_tau -- is an entry of one
+// of a few 256-entry tables, built once per launch.  More distinct values than CHAIN_TAB_MAX: the launch decodes record by record.
+constexpr int CHAIN_TAB_MAX = 4;
+constexpr int CHAIN_TAB_N = 257; // entries of a table: the 256 pixel bytes, and the entry of a lane beyond the frame (below)
 
 // exact floor(a/b) for a >= 0, b > 0: equals c10::div_floor_floating (whose fmod / re-divide /
 // "+1 if frac > 0.5" steps exist to return exactly this) without the fmod loop.
@@ -131,6 +136,18 @@ __device__ __forceinline__ double lane_value_d(double v, int idx)
     const unsigned long long u = (unsigned long long)__double_as_longlong(v);
     return __longlong_as_double((long long)(((unsigned long long)lane_value((uint32_t)(u >> 32), idx) << 32) | lane_value((uint32_t)u, idx)));
 }
+// min over the wave's 64 lanes (every lane active) as a scalar
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t u)
+{
+#define V2E_DPP_SELF(v, ctrl) ((uint32_t)__builtin_amdgcn_update_dpp((int)(v), (int)(v), (ctrl), 0xf, 0xf, false))
+    u = min(u, V2E_DPP_SELF(u, 0xB1));  // quad_perm [1,0,3,2]
+    u = min(u, V2E_DPP_SELF(u, 0x4E));  // quad_perm [2,3,0,1]
+    u = min(u, V2E_DPP_SELF(u, 0x141)); // row_half_mirror
+    u = min(u, V2E_DPP_SELF(u, 0x140)); // row_mirror
+#undef V2E_DPP_SELF
+    return min(min((uint32_t)__builtin_amdgcn_readlane((int)u, 0), (uint32_t)__builtin_amdgcn_readlane((int)u, 16)),
+               min((uint32_t)__builtin_amdgcn_readlane((int)u, 32), (uint32_t)__builtin_amdgcn_readlane((int)u, 48)));
+}
 __device__ __forceinline__ void store_event_wt(float4 *ev_clip, unsigned long long row, float t, float x, float y, float pol)
 {
     if (row < 0x7000000ull) { // byte offset below 2^31
@@ -177,6 +194,7 @@ struct ChainArgs {
     int prio;                         // wave priority of the chain (3: it outranks the emission waves sharing its SIMDs)
     int bar_light;                    // the redo rendezvous without release / acquire fences (the maxima rows are atomics)
     int lockstep;                     // redo passes take the frame(s) right behind a rule-on frame in lock-step (see k_chain)
+    int tables;                       // !FUSED: decode records through per-launch tables where the launch's frames allow it (V2E_AMD_CHAIN_TABLES=0: never)
     unsigned long long *dbg;          // dev tool: [ngroups][16] wall-clock stamps of one launch, or nullptr
     unsigned long long *const *stamp_pp; // *stamp_pp: the run's [launch][2] time stamps (v2e_emu_launch_stamps) or nullptr
     int lidx;                         // this launch's index in the run
@@ -380,6 +398,8 @@ void k_chain(KArgs a_in, ChainArgs ca)
     __shared__ double s_lutI[256];            // FUSED: and the pass's frame scalars
     __shared__ double s_dtau[FUSED ? CHAIN_K_MAX : 1], s_shot[FUSED ? CHAIN_K_MAX : 1];
     __shared__ float s_dtime[FUSED ? CHAIN_K_MAX : 1];
+    // !FUSED: the launch's decode tables (CHAIN_TAB_MAX above), entry = (1 - eps, eps * L) of a pixel byte under one dt_over_tau
+    __shared__ double2 s_tab[FUSED ? 1 : CHAIN_TAB_MAX * CHAIN_TAB_N];
     constexpr bool U8 = sizeof(FT) == 1;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int g = blockIdx.x;
@@ -455,8 +475,25 @@ void k_chain(KArgs a_in, ChainArgs ca)
         double dq_om[CHAIN_SUB], dq_el[CHAIN_SUB];
         float dq_dl[CHAIN_SUB];
         uint32_t dq_sb[CHAIN_SUB];
-        auto decode_sub = [&](const uint2 *r, const int kb, const double dtau_v) __attribute__((always_inline)) {
+        // Table path (use_tab, launch-uniform): tix_v, lane k = the table of frame k of the pass as an offset into s_tab; a record is
+        // then one scalar lane read, the entry's address, one 16-byte LDS read and the shot bits' shift.  A lane beyond the frame (its
+        // records are zero: never loaded) reads entry 256 of the table, (1, 0): what the zero record decodes to below.
+        bool use_tab = false;
+        const uint32_t inv_px = valid ? 0u : 256u;
+        auto decode_sub = [&](const uint2 *r, const int kb, const double dtau_v, const uint32_t tix_v) __attribute__((always_inline)) {
             if (FUSED) return;
+            if (use_tab) {
+#pragma unroll
+                for (int j = 0; j < CHAIN_SUB; ++j) {
+                    const uint32_t toff = (uint32_t)__builtin_amdgcn_readlane((int)tix_v, (kb + j) & (WAVE - 1));
+                    const double2 e = s_tab[toff + ((r[j].y & 0xFFu) | inv_px)];
+                    dq_om[j] = e.x;
+                    dq_el[j] = e.y;
+                    dq_dl[j] = __uint_as_float(r[j].x);
+                    dq_sb[j] = (r[j].y >> 5) & (CNT_SHOT_ON | CNT_SHOT_OFF);
+                }
+                return;
+            }
 #pragma unroll
             for (int j = 0; j < CHAIN_SUB; ++j) { // (a frame beyond the pass decodes to values nothing reads)
                 const uint4 rc = decode_rec(r[j], dtau_v, (kb + j) & (WAVE - 1));
@@ -524,9 +561,42 @@ void k_chain(KArgs a_in, ChainArgs ca)
         else
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(b), "+v"(lp), "+v"(tsm), "+v"(thp), "+v"(thn), "+v"(gM_v), "+v"(mon_own), "+v"(mon_prev),
                          "+v"(dtau_own), "+v"(dtau_prev), "+v"(tab_L), "+v"(tab_I) : : "memory");
-        if (!FUSED && clip == (int)blockIdx.y) { // (the tables stay in LDS for the workgroup's later clips)
-            s_lutL[tid] = tab_L;
-            s_lutI[tid] = tab_I;
+        // lane k: the decode table (offset into s_tab) of frame k of this launch / of the previous one
+        uint32_t tix_own = 0u, tix_prev = 0u;
+        if (!FUSED) {
+            if (clip == (int)blockIdx.y) { // (the lin-log tables stay in LDS for the workgroup's later clips)
+                s_lutL[tid] = tab_L;
+                s_lutI[tid] = tab_I;
+            }
+            if (ca.tables) {
+                // The distinct dt_over_tau bit patterns of the frames this launch may decode -- its own and, where a redo is possible,
+                // its predecessor's -- in lane order: every wave of every workgroup finds the same ones from the same FrameCtl rows.
+                // Thread t builds entry t of each value's table with decode_frame_record's and decode_sub's own float64 operations
+                // (eps and L through the 16-byte record's bit layout, as the record-by-record decode reads them back).
+                unsigned long long todo_o = __ballot(lane < ca.nf), todo_p = __ballot(!own && lane < ca.pnf);
+                const long long bits_o = __double_as_longlong(dtau_own), bits_p = __double_as_longlong(dtau_prev);
+                int nt = 0;
+                while ((todo_o | todo_p) != 0ull && nt < CHAIN_TAB_MAX) {
+                    const double dtau = todo_o != 0ull ? lane_value_d(dtau_own, (int)__builtin_ctzll(todo_o))
+                                                       : lane_value_d(dtau_prev, (int)__builtin_ctzll(todo_p));
+                    const long long bits = __double_as_longlong(dtau);
+                    if (bits_o == bits) tix_own = (uint32_t)(nt * CHAIN_TAB_N); // (a lane beyond the launch: an index nothing reads)
+                    if (bits_p == bits) tix_prev = (uint32_t)(nt * CHAIN_TAB_N);
+                    todo_o &= ~__ballot(bits_o == bits);
+                    todo_p &= ~__ballot(bits_p == bits);
+                    const double L = (double)(float)(a.log_input ? (double)tid : (double)tab_L);
+                    double eps = 0.0;
+                    if (a.has_cutoff) {
+                        eps = tab_I * dtau;
+                        if (eps > 1.0) eps = 1.0;
+                    }
+                    eps = __longlong_as_double(__double_as_longlong(eps) & 0x3FFFFFFFFFFFFFFFll);
+                    s_tab[nt * CHAIN_TAB_N + tid] = make_double2(1.0 - eps, a.has_cutoff ? eps * L : L);
+                    ++nt;
+                }
+                use_tab = (todo_o | todo_p) == 0ull;
+                if (tid < CHAIN_TAB_MAX) s_tab[tid * CHAIN_TAB_N + 256] = make_double2(1.0, 0.0);
+            }
             __syncthreads();
         }
         if (FUSED) {
@@ -607,11 +677,14 @@ void k_chain(KArgs a_in, ChainArgs ca)
             else { fs = ca.pf0; fn = ca.pnf; gM_dst = ca.gM_prev + ((size_t)round * ca.n_clips + clip) * ca.K; }
             const int fs_slot = own ? ca.slot_f0 : ca.slot_pf0;
             const double dtau_v = own ? dtau_own : dtau_prev;
+            const uint32_t tix_v = own ? tix_own : tix_prev;
             if (redone) { // a redo pass, or the own pass after one: its inputs replace what the prologue staged
                 fill_scalars(fs, fn);
                 stage(wrap_slot(fs_slot + c0), fn - c0);
             }
             const uint32_t mon_v = own ? mon_own : mon_prev;
+            // the smallest rule threshold of the pass's frames (lanes beyond them hold 0xFFFFFFFF): the light body's coarse speculation test
+            const uint32_t mon_min = (!FUSED && a.has_refr) ? wave_min_u32(mon_v) : 0u;
             // checkpoints of this pass go to the set of the launch whose frames it runs
             void *const ck_base = own ? ca.ckc_base : ca.ckp_base;
             void *const ck_lp = own ? ca.ckc_lp : ca.ckp_lp;
@@ -768,7 +841,7 @@ void k_chain(KArgs a_in, ChainArgs ca)
                     if (++sl == ca.D) sl = 0;
                 }
             };
-            decode_sub(st, c0, dtau_v);
+            decode_sub(st, c0, dtau_v, tix_v);
             fetch_next(c0 + CHAIN_SUB);
             for (int k0 = c0; k0 < fn; k0 += CHAIN_SUB) {
                 if (ck_base && k0 > c0 && valid) { // state before frame k0
@@ -807,11 +880,17 @@ void k_chain(KArgs a_in, ChainArgs ca)
                 if (!FUSED) {
                     const int rem = fn - k0 - CHAIN_SUB; // frames of the pass behind this sub-pass
                     // the next sub-pass's records, decoded: their table reads in flight together, one wait
-                    if (rem > 0) decode_sub(nx, k0 + CHAIN_SUB, dtau_v);
+                    if (rem > 0) decode_sub(nx, k0 + CHAIN_SUB, dtau_v, tix_v);
                     // the light body's speculation check, for the sub-pass's frames at once: the frames after the last exact one that some
                     // lane of the wave took to the rule threshold publish the wave's max, as the general body does per frame (one branch,
                     // rarely taken)
-                    if (light && a.has_refr) {
+                    // -- behind ONE coarse test: no frame reaches its own threshold without reaching the pass's smallest one, so a wave
+                    // none of whose lanes took any of the sub-pass's counts (zero for frames beyond the pass) to mon_min has nothing
+                    // to publish; what is published is decided by the exact per-frame code, as before
+                    uint32_t mag_max = magq[0];
+#pragma unroll
+                    for (int j = 1; j < CHAIN_SUB; ++j) mag_max = max(mag_max, magq[j]);
+                    if (light && a.has_refr && __builtin_expect(__ballot(mag_max >= mon_min) != 0ull, 0)) {
                         unsigned long long hit[CHAIN_SUB], any = 0ull;
 #pragma unroll
                         for (int j = 0; j < CHAIN_SUB; ++j) {

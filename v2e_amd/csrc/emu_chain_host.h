@@ -77,6 +77,14 @@ static bool chain_fused_records(const v2e_emu *h, int dtype, int nD)
     return fused_env >= 0 ? fused_env != 0 : !chain_small_grid(h);
 }
 
+// k_chain on k_ahead's records decodes them through per-launch tables (emu_chain.h, CHAIN_TAB_MAX) wherever a launch's frames take few
+// enough distinct dt_over_tau values; V2E_AMD_CHAIN_TABLES=0 keeps the record-by-record decode for every launch (A/B runs, tests)
+static bool chain_decode_tables()
+{
+    const char *e = getenv("V2E_AMD_CHAIN_TABLES"); // read per run, as V2E_AMD_CHAIN_FUSED is
+    return !(e && atoi(e) == 0);
+}
+
 // allon: every run-time feature switch of the frame loop is on (cutoff, leak, shot noise, refractory period: the v2e CLI
 // defaults) -> the instantiation without those tests; built for float64 state and uint8 frames (what that configuration has)
 static const void *chain_fn(bool f64, int dtype, bool fused, bool allon = false)
@@ -516,6 +524,7 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
     int last_emitted = -1; // the last emission slot this piece enqueued (joined at the end)
     const bool allon = a_in.has_cutoff && a_in.do_leak && a_in.do_shot && a_in.has_refr;
     const void *kfn = chain_fn(p->f64_state != 0, dtype, fused_rec, allon);
+    const int tables = (!fused_rec && chain_decode_tables()) ? 1 : 0;
     for (int L = 0; L < nL; ++L) {
         const ChainLaunch &pl = plan[L];
         const bool tail = pl.nf == 0;
@@ -554,6 +563,7 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
         ca.store_out = tail && in != 0;
         ca.prio = 3;      // wave priority of the chain (measured against 0 in round 3)
         ca.bar_light = 1; // the fence-free rendezvous (round 4; the fenced one of round 3 is still in clip_barrier)
+        ca.tables = tables;
         ca.lockstep = 0;  // lock-step redo passes (emu_chain.h, V2E_CHAIN_LOCKSTEP): 10.4-10.6 against 10.8-11.0 Gev/s on the benchmark clip (round 4)
         ca.dbg = (h->dbg && L == nB / 2) ? h->dbg : nullptr;
         ca.stamp_pp = r.stamp_slot; ca.lidx = std::min(L, STAMP_LAUNCHES - 1);
