@@ -17,7 +17,7 @@ def _free_port():
     return p
 
 
-from tests.bench_stub import StubEmulator as _StubEmulator, rows as _rows  # noqa: E402
+from tests.bench_stub import StubEmulator as _StubEmulator, StubPending as _StubPending, rows as _rows  # noqa: E402
 
 
 def _rows_runs(n, rank, step):
@@ -289,12 +289,12 @@ class _StubSloMoPipeline:
     """VideoToEvents with the two device stages stubbed: upsample() = a deterministic function of each source pair, the emulator a
     recorder.  Everything else (sharding, gather, frame order, times) is v2e_amd.pipeline's code."""
 
-    def __new__(cls, U, batch_size):
+    def __new__(cls, U, batch_size, asynchronous=False):
         from v2e_amd.pipeline import VideoToEvents
 
         class P(VideoToEvents):
             def __init__(self):
-                self.U, self.batch_size, self.seen = U, batch_size, None
+                self.U, self.batch_size, self.seen, self.async_calls = U, batch_size, None, 0
                 outer = self
 
                 class Emu:
@@ -305,7 +305,12 @@ class _StubSloMoPipeline:
                         else:
                             outer.seen = (torch.cat((outer.seen[0], frames)), np.concatenate((outer.seen[1], np.asarray(times))))
                         return torch.zeros((int(frames.sum()) % 7, 4)), np.asarray([int(f.sum()) % 5 for f in frames])
-                self.emu = Emu()
+
+                class AsyncEmu(Emu):
+                    def generate_events_batch_async(self, frames, times, return_device=False):
+                        outer.async_calls += 1
+                        return _StubPending(*self.generate_events_batch(frames, times, return_device))
+                self.emu = AsyncEmu() if asynchronous else Emu()
 
             def upsample(self, frames_u8):
                 n = int(frames_u8.shape[0]) - 1
@@ -317,7 +322,7 @@ class _StubSloMoPipeline:
         return P()
 
 
-def _slomo_shard_worker(rank, world, port, q, n_src, U):
+def _slomo_shard_worker(rank, world, port, q, n_src, U, asynchronous=False):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -338,16 +343,30 @@ def _slomo_shard_worker(rank, world, port, q, n_src, U):
     # in chunks of 3 and of 1 source pairs (the owner's DVS stage on chunk c while chunk c + 1 is interpolated; ragged last chunk, chunks
     # with fewer pairs than ranks): the same frames in the same order with the same times, the same per-frame counts
     for cp in (3, 1):
-        chunked = _StubSloMoPipeline(U, 2)
+        chunked = _StubSloMoPipeline(U, 2, asynchronous)
         ev3, c3, n3 = chunked.run(frames, 1 / 30, group=dist.group.WORLD, owner=world - 1, chunk_pairs=cp)
         ok &= n3 == n1
         if rank == world - 1:
             ok &= torch.equal(chunked.seen[0], single.seen[0]) and np.array_equal(chunked.seen[1], single.seen[1]) and np.array_equal(c3, c1)
+            ok &= chunked.async_calls == (len(range(0, n_src - 1, cp)) if asynchronous else 0)
         else:
             ok &= ev3 is None and c3 is None and chunked.seen is None
     q.put((rank, bool(ok)))
     dist.barrier()
     dist.destroy_process_group()
+
+
+def _run_slomo_shard_workers(world, n_src, U, asynchronous):
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_slomo_shard_worker, args=(r, world, port, q, n_src, U, asynchronous)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = dict(q.get(timeout=180) for _ in range(world))
+    for p in procs:
+        p.join(timeout=60)
+    assert res == {r: True for r in range(world)}
 
 
 @pytest.mark.parametrize("world,n_src,U", [(2, 9, 3), (4, 11, 2), (4, 3, 5)])
@@ -358,13 +377,12 @@ def test_slomo_pair_sharding_reproduces_the_single_rank_clip(world, n_src, U):
     P = n_src - 1
     blocks = [pair_shard(P, world, r) for r in range(world)]
     assert blocks[0][0] == 0 and blocks[-1][1] == P and all(blocks[i][1] == blocks[i + 1][0] for i in range(world - 1))
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_slomo_shard_worker, args=(r, world, port, q, n_src, U)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = dict(q.get(timeout=180) for _ in range(world))
-    for p in procs:
-        p.join(timeout=60)
-    assert res == {r: True for r in range(world)}
+    _run_slomo_shard_workers(world, n_src, U, False)
+
+
+@pytest.mark.parametrize("world,n_src,U", [(2, 9, 3), (4, 11, 2), (4, 3, 5)])
+def test_chunked_sharding_through_an_asynchronous_emulator(world, n_src, U):
+    """The chunked runs again with an emulator that offers generate_events_batch_async (a handle whose result() is what
+    generate_events_batch gives): the owner enqueues every chunk and reads the results behind it -- the same frames, order, times
+    and counts, None on the other ranks."""
+    _run_slomo_shard_workers(world, n_src, U, True)

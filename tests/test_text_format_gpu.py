@@ -79,7 +79,8 @@ def test_aedat2_noise_bit_per_frame_of_a_run():
     by tests/test_sinks.py), concatenated."""
     import torch
     from v2e_amd import _capi
-    from v2e_amd.sinks import _frame_recs, _ptr, _AEDAT2_LAYOUT, pack_aedat2
+    from v2e_amd._capi import ptr as _ptr
+    from v2e_amd.sinks import _frame_recs, _AEDAT2_LAYOUT, pack_aedat2
     import ctypes as C
     z = np.load(os.path.join(GOLDEN, "sinks.npz"))
     ev = torch.from_numpy(z["ev_346x260"]).cuda()

@@ -19,6 +19,47 @@ def _upsample_flow_chunks(P, bs):
     return out
 
 
+def _upsample_auto_flow_chunks(P, bs):
+    """The same calls as the auto_upsample loop has formed them: a list made before the loop."""
+    fc = bs * max(1, 64 // bs)
+    return [(f0, min(f0 + fc, P)) for f0 in range(0, P, fc)]
+
+
+@pytest.mark.parametrize("P", [1, 63, 64, 65, 130])
+@pytest.mark.parametrize("bs", [1, 2, 8, 5])
+def test_flow_chunks_are_those_of_both_upsample_loops(P, bs):
+    from v2e_amd.planning import flow_chunks, last_flow_chunk
+    got = flow_chunks(P, bs)
+    assert got == _upsample_flow_chunks(P, bs) == _upsample_auto_flow_chunks(P, bs)
+    assert got[-1] == last_flow_chunk(P, bs) and all(type(v) is int for c in got for v in c)
+
+
+@pytest.mark.parametrize("U", range(2, 10))
+def test_time_points_of_a_factor(U):
+    from v2e_amd.planning import time_points
+    got = time_points(U)
+    assert got == [(k + 0.5) / U for k in range(U)] and all(type(t) is float for t in got)
+
+
+def test_planning_needs_no_torch():
+    """The planning module, loaded from its file (the package imports torch), imports and runs where torch is not imported."""
+    import os
+    import subprocess
+    import sys
+    import v2e_amd.planning as planning
+    code = ("import importlib.util, sys\n"
+            "spec = importlib.util.spec_from_file_location('planning', sys.argv[1])\n"
+            "m = importlib.util.module_from_spec(spec)\n"
+            "spec.loader.exec_module(m)\n"
+            "assert 'torch' not in sys.modules\n"
+            "t = m.interp_frame_times(21, None, 0.1, 8, factors=[5, 3, 9])\n"
+            "ts, tab, cuts = m.auto_sample_table([5, 3, 9], 20, 8)\n"
+            "assert len(t) == len(tab) == cuts[-1] == 5 * 8 + 3 * 8 + 9 * 4 and len(ts) == 5 + 3 + 9\n"
+            "assert 'torch' not in sys.modules and 'v2e_amd' not in sys.modules\n")
+    r = subprocess.run([sys.executable, "-c", code, os.path.abspath(planning.__file__)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
 @pytest.mark.parametrize("P,bs,cp", CASES)
 def test_chunks_cover_the_pairs_on_flow_chunk_boundaries(P, bs, cp):
     from v2e_amd.pipeline import flow_chunk_pairs, last_flow_chunk, stream_chunks

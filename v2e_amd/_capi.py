@@ -234,6 +234,17 @@ def lib():
     return l
 
 
+def ptr(t):
+    """The device (or pinned host) address of a tensor as the void pointer the entry points take; None stays None (NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream_ptr(device):
+    """The current torch stream of `device` as the hipStream_t the entry points take."""
+    import torch  # (not at module level: the binding itself loads without torch)
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 def check(rc, what=""):
     if rc != 0:
         msg = lib().v2e_last_error()

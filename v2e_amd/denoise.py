@@ -31,15 +31,11 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._capi import check
+from ._capi import check, ptr, stream_ptr
 
 MAX_TAUS = 256
 NEIGHBOURS = 8
 DEFAULT_ROWS_PER_PASS = 1 << 25
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _check_taus(taus):
@@ -220,7 +216,7 @@ class DenoiseSweep(object):
             return {"n": zero, "n_bad": zero.clone(), "mask": None if keep is None else torch.zeros((0,), dtype=torch.bool, device=dev)}
         rows = rows.to(dev).contiguous()
         lib = _capi.lib()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = stream_ptr(dev)
         H, W, T = self.height, self.width, len(self.taus)
         lab = None if labels is None else labels.to(dev, non_blocking=True).to(torch.uint8).contiguous()
         lb = None if bounds is None else self._upload(bounds)
@@ -232,15 +228,15 @@ class DenoiseSweep(object):
             ev = rows[r0:r0 + m]
             keep_p = None if mask is None else C.c_void_p(mask.data_ptr() + r0)
             keys = torch.empty((m,), dtype=torch.int64, device=dev)
-            check(lib.v2e_denoise_keys(_ptr(ev), m, H, W, _ptr(keys), keep_p, stream), "v2e_denoise_keys")
+            check(lib.v2e_denoise_keys(ptr(ev), m, H, W, ptr(keys), keep_p, stream), "v2e_denoise_keys")
             skeys = torch.sort(keys)[0]
             del keys
-            check(lib.v2e_denoise_segments(_ptr(skeys), m, H, W, _ptr(st["seg"]), _ptr(cnt), stream), "v2e_denoise_segments")
-            check(lib.v2e_denoise_ages(_ptr(ev), m, H, W, _ptr(skeys), _ptr(st["seg"]), _ptr(st["last_t"]), _ptr(st["taus"]), T,
-                                       None if lab is None else C.c_void_p(lab.data_ptr() + r0), _ptr(lb),
-                                       0 if lb is None else int(lb.shape[0]), r0, _ptr(st["hist"]), keep_p, k, tau, stream),
+            check(lib.v2e_denoise_segments(ptr(skeys), m, H, W, ptr(st["seg"]), ptr(cnt), stream), "v2e_denoise_segments")
+            check(lib.v2e_denoise_ages(ptr(ev), m, H, W, ptr(skeys), ptr(st["seg"]), ptr(st["last_t"]), ptr(st["taus"]), T,
+                                       None if lab is None else C.c_void_p(lab.data_ptr() + r0), ptr(lb),
+                                       0 if lb is None else int(lb.shape[0]), r0, ptr(st["hist"]), keep_p, k, tau, stream),
                   "v2e_denoise_ages")
-            check(lib.v2e_denoise_map_update(_ptr(ev), _ptr(skeys), _ptr(st["seg"]), H, W, _ptr(st["last_t"]), stream),
+            check(lib.v2e_denoise_map_update(ptr(ev), ptr(skeys), ptr(st["seg"]), H, W, ptr(st["last_t"]), stream),
                   "v2e_denoise_map_update")
             self.passes += 1
         st["n_bad"] += cnt[1]

@@ -24,14 +24,12 @@ import ctypes as C
 import torch
 import torch.distributed as dist
 
+from ._capi import stream_ptr
+
 
 def clips_of_rank(n_clips, world, rank):
     """clip c runs on rank c mod world (round-robin; clips are independent)."""
     return [c for c in range(n_clips) if c % world == rank]
-
-
-def _stream_ptr(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def pack_events64(ev, out=None):
@@ -43,7 +41,7 @@ def pack_events64(ev, out=None):
         return out
     if ev.is_cuda:
         from . import _capi
-        _capi.check(_capi.lib().v2e_events_pack64(C.c_void_p(ev.data_ptr()), C.c_void_p(out.data_ptr()), n, _stream_ptr(ev.device)),
+        _capi.check(_capi.lib().v2e_events_pack64(C.c_void_p(ev.data_ptr()), C.c_void_p(out.data_ptr()), n, stream_ptr(ev.device)),
                     "v2e_events_pack64")
     else:  # CPU tensors (gloo tests): the same bit layout with torch ops
         e = ev.contiguous()
@@ -62,7 +60,7 @@ def unpack_events64(words):
     if words.is_cuda:
         from . import _capi
         w = words.contiguous()
-        _capi.check(_capi.lib().v2e_events_unpack64(C.c_void_p(w.data_ptr()), C.c_void_p(ev.data_ptr()), n, _stream_ptr(words.device)),
+        _capi.check(_capi.lib().v2e_events_unpack64(C.c_void_p(w.data_ptr()), C.c_void_p(ev.data_ptr()), n, stream_ptr(words.device)),
                     "v2e_events_unpack64")
     else:
         w = words.contiguous()
@@ -95,7 +93,7 @@ def pack_events32(ev, payload=None, runs=None, cap_runs=None, scratch=None):
             scratch = torch.empty((words,), dtype=torch.int32, device=dev)
         _capi.check(lib.v2e_events_pack32(C.c_void_p(ev.data_ptr()) if n else None, n, C.c_void_p(payload.data_ptr()),
                                           C.c_void_p(runs.data_ptr()), int(min(cap_runs, runs.numel() - 1)),
-                                          C.c_void_p(scratch.data_ptr()), _stream_ptr(dev)), "v2e_events_pack32")
+                                          C.c_void_p(scratch.data_ptr()), stream_ptr(dev)), "v2e_events_pack32")
         return payload, runs, scratch
     e = ev.contiguous()
     tb = e[:, 0].contiguous().view(torch.int32)
@@ -128,7 +126,7 @@ def unpack_events32(payload, runs, n=None):
     if payload.is_cuda:
         from . import _capi
         _capi.check(_capi.lib().v2e_events_unpack32(C.c_void_p(payload.data_ptr()), n, C.c_void_p(runs.data_ptr()),
-                                                    C.c_void_p(ev.data_ptr()), _stream_ptr(payload.device)), "v2e_events_unpack32")
+                                                    C.c_void_p(ev.data_ptr()), stream_ptr(payload.device)), "v2e_events_unpack32")
         return ev
     R = int(runs[0]) & 0xFFFFFFFF
     tbl = runs[1:1 + R]

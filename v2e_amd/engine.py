@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._capi import EmuParams, FrameRec, check
+from ._capi import EmuParams, FrameRec, check, ptr
 
 _DT = {torch.uint8: _capi.DT_U8, torch.float32: _capi.DT_F32, torch.float64: _capi.DT_F64}
 
@@ -87,10 +87,6 @@ _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 if _raw_stream is None:  # older / other torch builds
     def _raw_stream(idx):
         return torch.cuda.current_stream(idx).cuda_stream
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _dbl_array(vals):
@@ -165,9 +161,9 @@ class EmuEngine:
         self.pos_thres = torch.zeros(shp, dtype=torch.float32, device=dev)
         self.neg_thres = torch.zeros(shp, dtype=torch.float32, device=dev)
         self.noise_rate = torch.zeros(shp, dtype=torch.float32, device=dev)
-        check(self.lib.v2e_emu_bind_state(self._h, _ptr(self.lp), _ptr(self.base), _ptr(self.ts_mem),
-                                          _ptr(self.pos_thres), _ptr(self.neg_thres),
-                                          _ptr(self.noise_rate)), "v2e_emu_bind_state")
+        check(self.lib.v2e_emu_bind_state(self._h, ptr(self.lp), ptr(self.base), ptr(self.ts_mem),
+                                          ptr(self.pos_thres), ptr(self.neg_thres),
+                                          ptr(self.noise_rate)), "v2e_emu_bind_state")
 
     def plane(self, t, clip=0):
         """[H,W] view of a state plane."""
@@ -200,30 +196,30 @@ class EmuEngine:
     # ------------------------------------------------------------ calls
     def init_state(self, P, frame_dev, t_frame, thres_pos=None, thres_neg=None, noise_rate=None):
         self._check_frame(frame_dev, self.n_clips)
-        check(self.lib.v2e_emu_init_state(self._h, C.byref(P), _ptr(frame_dev), _DT[frame_dev.dtype],
-                                          float(t_frame), _ptr(thres_pos), _ptr(thres_neg), _ptr(noise_rate),
+        check(self.lib.v2e_emu_init_state(self._h, C.byref(P), ptr(frame_dev), _DT[frame_dev.dtype],
+                                          float(t_frame), ptr(thres_pos), ptr(thres_neg), ptr(noise_rate),
                                           self.stream), "v2e_emu_init_state")
 
     def count(self, P, frame_dev, t_prev, t_frame, frame_idx, leak_randn=None, shot_rand=None):
         self._check_frame(frame_dev, self.n_clips)
-        check(self.lib.v2e_emu_count(self._h, C.byref(P), _ptr(frame_dev), _DT[frame_dev.dtype],
+        check(self.lib.v2e_emu_count(self._h, C.byref(P), ptr(frame_dev), _DT[frame_dev.dtype],
                                      _dbl_array(t_prev), _dbl_array(t_frame), int(frame_idx),
-                                     _ptr(leak_randn), _ptr(shot_rand), self.stream), "v2e_emu_count")
+                                     ptr(leak_randn), ptr(shot_rand), self.stream), "v2e_emu_count")
 
     def set_csdvs(self, surround_plane):
         """cs_surround_frame plane [n_clips][npx_pad] (state dtype) that count() subtracts; None switches CSDVS off."""
-        check(self.lib.v2e_emu_set_csdvs(self._h, _ptr(surround_plane)), "v2e_emu_set_csdvs")
+        check(self.lib.v2e_emu_set_csdvs(self._h, ptr(surround_plane)), "v2e_emu_set_csdvs")
 
     def lp_preview(self, P, frame_dev, t_prev, t_frame, frame_idx, lp_out):
         """The coming frame's lp_log_frame into lp_out, the state untouched (v2e_emu_lp_preview)."""
         self._check_frame(frame_dev, self.n_clips)
-        check(self.lib.v2e_emu_lp_preview(self._h, C.byref(P), _ptr(frame_dev), _DT[frame_dev.dtype], _dbl_array(t_prev),
-                                          _dbl_array(t_frame), int(frame_idx), _ptr(lp_out), self.stream), "v2e_emu_lp_preview")
+        check(self.lib.v2e_emu_lp_preview(self._h, C.byref(P), ptr(frame_dev), _DT[frame_dev.dtype], _dbl_array(t_prev),
+                                          _dbl_array(t_frame), int(frame_idx), ptr(lp_out), self.stream), "v2e_emu_lp_preview")
 
     def csdvs_update(self, p_plane, h_plane, h_scratch, alpha_p, alpha_h, num_steps, stop):
         """EventEmulator._update_csdvs's stepping loop on device planes (v2e_csdvs_update); returns the steps taken."""
         steps = C.c_int(0)
-        check(self.lib.v2e_csdvs_update(_ptr(p_plane), _ptr(h_plane), _ptr(h_scratch), self.H, self.W, 1 if self.f64_state else 0,
+        check(self.lib.v2e_csdvs_update(ptr(p_plane), ptr(h_plane), ptr(h_scratch), self.H, self.W, 1 if self.f64_state else 0,
                                         float(alpha_p), float(alpha_h), int(num_steps), float(stop), C.byref(steps), None,
                                         self.stream), "v2e_csdvs_update")
         return int(steps.value)
@@ -231,20 +227,20 @@ class EmuEngine:
     def set_pnoise(self, pn_plane, randn_tape=None):
         """photoreceptor_noise_arr plane [n_clips][npx_pad] float64 (+ the frame's torch.randn draws in tape mode) for
         the next count(); None switches the feature off."""
-        check(self.lib.v2e_emu_set_pnoise(self._h, _ptr(pn_plane), _ptr(randn_tape)), "v2e_emu_set_pnoise")
+        check(self.lib.v2e_emu_set_pnoise(self._h, ptr(pn_plane), ptr(randn_tape)), "v2e_emu_set_pnoise")
 
     def set_model_state_planes(self, planes):
         """Three float64 planes [n_clips][npx_pad] (log_new_frame, c_minus_s_frame, diff_frame) every count() fills from
         now on; None switches it off (v2e_emu_set_model_state_planes)."""
         a, b, c = planes if planes is not None else (None, None, None)
-        check(self.lib.v2e_emu_set_model_state_planes(self._h, _ptr(a), _ptr(b), _ptr(c)), "v2e_emu_set_model_state_planes")
+        check(self.lib.v2e_emu_set_model_state_planes(self._h, ptr(a), ptr(b), ptr(c)), "v2e_emu_set_model_state_planes")
 
     def set_probes(self, pixel_index, out_dev):
         """The next run() records the single-pixel model states of the pixels `pixel_index` (row * W + col each) into out_dev, a
         float64 device tensor [F][len(pixel_index)][PROBE_FIELDS] (v2e_emu_set_probes; one shot); None / empty cancels."""
         n = 0 if pixel_index is None else len(pixel_index)
         arr = (C.c_int32 * max(n, 1))(*[int(v) for v in (pixel_index or ())])
-        check(self.lib.v2e_emu_set_probes(self._h, arr, n, _ptr(out_dev) if n else None), "v2e_emu_set_probes")
+        check(self.lib.v2e_emu_set_probes(self._h, arr, n, ptr(out_dev) if n else None), "v2e_emu_set_probes")
 
     def probe_buffer(self, n_frames, n_probes, which=0):
         """Device float64 [F][P][PROBE_FIELDS] for set_probes, cached per (F, P, set) like alloc_recs: the hipGraph of a probed run
@@ -271,8 +267,8 @@ class EmuEngine:
         return self._side_streams[name]
 
     def shot(self, P, frame_dev, frame_idx, shot_rand):
-        check(self.lib.v2e_emu_shot(self._h, C.byref(P), _ptr(frame_dev), _DT[frame_dev.dtype],
-                                    int(frame_idx), _ptr(shot_rand), self.stream), "v2e_emu_shot")
+        check(self.lib.v2e_emu_shot(self._h, C.byref(P), ptr(frame_dev), _DT[frame_dev.dtype],
+                                    int(frame_idx), ptr(shot_rand), self.stream), "v2e_emu_shot")
 
     def read_rec(self, frame_idx):
         recs = (FrameRec * self.n_clips)()
@@ -284,7 +280,7 @@ class EmuEngine:
 
     def rank(self, P, frame_idx, ts_table=None):
         n_ts = 0 if ts_table is None else int(ts_table.shape[-1])
-        check(self.lib.v2e_emu_rank(self._h, C.byref(P), int(frame_idx), _ptr(ts_table), n_ts, self.stream),
+        check(self.lib.v2e_emu_rank(self._h, C.byref(P), int(frame_idx), ptr(ts_table), n_ts, self.stream),
               "v2e_emu_rank")
 
     def read_iter_counts(self, frame_idx, n_iters):
@@ -312,11 +308,11 @@ class EmuEngine:
         off = None
         if ev_offset0 is not None:
             off = (C.c_uint64 * self.n_clips)(*[int(v) for v in ev_offset0])
-        check(self.lib.v2e_emu_emit(self._h, C.byref(P), int(frame_idx), _ptr(ts_table), n_ts, _ptr(events),
+        check(self.lib.v2e_emu_emit(self._h, C.byref(P), int(frame_idx), ptr(ts_table), n_ts, ptr(events),
                                     int(events.shape[1]), off, self.stream), "v2e_emu_emit")
 
     def permute(self, events_in, events_out, idx_dev, row0, n):
-        check(self.lib.v2e_emu_permute(self._h, _ptr(events_in), _ptr(events_out), _ptr(idx_dev), int(row0),
+        check(self.lib.v2e_emu_permute(self._h, ptr(events_in), ptr(events_out), ptr(idx_dev), int(row0),
                                        int(n), self.stream), "v2e_emu_permute")
 
     def frame(self, P, frame, t_prev, t_frame, frame_idx, events):
@@ -329,7 +325,7 @@ class EmuEngine:
                                                                  np.dtype(np.float64): _capi.DT_F64}[frame.dtype]
             n_el = frame.size
         else:
-            fp, on_host, dt, n_el = _ptr(frame), 0, _DT[frame.dtype], frame.numel()
+            fp, on_host, dt, n_el = ptr(frame), 0, _DT[frame.dtype], frame.numel()
         if n_el != self.npx:
             raise ValueError("frame has %d elements, expected %d x %d" % (n_el, self.H, self.W))
         out8 = (C.c_uint32 * 8)()
@@ -341,7 +337,7 @@ class EmuEngine:
             if buf is not None:
                 check(self.lib.v2e_emu_frame_host_rows(self._h, C.c_void_p(buf.ptr), buf.cap), "v2e_emu_frame_host_rows")
             rc = self.lib.v2e_emu_frame(self._h, C.byref(P), fp, on_host, dt, float(t_prev), float(t_frame), int(frame_idx),
-                                        _ptr(events), int(events.shape[1]), out8, C.byref(rows), self.stream)
+                                        ptr(events), int(events.shape[1]), out8, C.byref(rows), self.stream)
             if rc < 0:
                 check(rc, "v2e_emu_frame")
             ev = None
@@ -367,10 +363,10 @@ class EmuEngine:
         self._check_frame(frames_dev, F * self.n_clips)
         tp = np.ascontiguousarray(np.asarray(t_prev, dtype=np.float64).reshape(F * self.n_clips))
         tf = np.ascontiguousarray(np.asarray(t_frame, dtype=np.float64).reshape(F * self.n_clips))
-        check(self.lib.v2e_emu_run(self._h, C.byref(P), _ptr(frames_dev), _DT[frames_dev.dtype], F,
+        check(self.lib.v2e_emu_run(self._h, C.byref(P), ptr(frames_dev), _DT[frames_dev.dtype], F,
                                    tp.ctypes.data_as(C.POINTER(C.c_double)),
-                                   tf.ctypes.data_as(C.POINTER(C.c_double)), int(frame_idx0), _ptr(events),
-                                   int(events.shape[1]), _ptr(recs_dev), int(use_graph), self.stream),
+                                   tf.ctypes.data_as(C.POINTER(C.c_double)), int(frame_idx0), ptr(events),
+                                   int(events.shape[1]), ptr(recs_dev), int(use_graph), self.stream),
               "v2e_emu_run")
 
     def run_done_event(self):

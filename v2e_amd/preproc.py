@@ -7,14 +7,13 @@ is OpenCV 4.x's published 8-bit algorithm (modules/imgproc/src/resize.cpp, color
 oracle/preproc_oracle.py; the kernels (v2e_amd/csrc/preproc.hip) equal that restatement bit for bit.  Shrinking only (the
 INTER_AREA branch proper); a target larger than the source in either direction raises NotImplementedError.
 """
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
 from . import _capi
-from ._capi import check
+from ._capi import check, ptr, stream_ptr
 
 
 def area_tab(ssize, dsize):
@@ -49,10 +48,6 @@ def is_area_fast(ssize_wh, dsize_wh):
         scale = 1.0 / (float(d) / float(s))
         out.append(abs(scale - int(scale)) < np.finfo(np.float64).eps)
     return all(out)
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class Stage1:
@@ -105,16 +100,16 @@ class Stage1:
         x = x.contiguous()
         ih, iw = self.src_hw
         assert tuple(x.shape[1:3]) == (ih, iw) and (x.ndim == 3) == (self.cn == 1)
-        s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        s = stream_ptr(self.device)
         if self.resize:
             shape = (n, self.oh, self.ow) + ((3,) if self.cn == 3 else ())
             y = torch.empty(shape, dtype=torch.uint8, device=self.device)
             t = self.tabs or [None] * 6
-            check(self.lib.v2e_resize_area_u8(_ptr(x), _ptr(y), n, ih, iw, self.oh, self.ow, self.cn, *[_ptr(a) for a in t], s),
+            check(self.lib.v2e_resize_area_u8(ptr(x), ptr(y), n, ih, iw, self.oh, self.ow, self.cn, *[ptr(a) for a in t], s),
                   "v2e_resize_area_u8")
             x = y
         if self.cn == 3:
             g = torch.empty(tuple(x.shape[:3]), dtype=torch.uint8, device=self.device)
-            check(self.lib.v2e_bgr2gray_u8(_ptr(x), _ptr(g), n * int(x.shape[1]) * int(x.shape[2]), self.gray_shift, s), "v2e_bgr2gray_u8")
+            check(self.lib.v2e_bgr2gray_u8(ptr(x), ptr(g), n * int(x.shape[1]) * int(x.shape[2]), self.gray_shift, s), "v2e_bgr2gray_u8")
             x = g
         return x

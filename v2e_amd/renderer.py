@@ -199,7 +199,7 @@ class EventRenderer(object):
             ev = torch.from_numpy(host).to(dev)
             edge = host[[0, max(n - 2, 0)], 0] if self.exposure_mode == ExposureMode.DURATION else None
         lib = _capi.lib()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _capi.stream_ptr(dev)
         mode = self.exposure_mode
         bounds_dev = seg_dev = None
         n_bounds = n_seg = 0
@@ -301,7 +301,7 @@ class EventRenderer(object):
         if self.height is None or self.width is None:
             raise ValueError("height and width not set for the output frames")
         dev, lib, mode = self.device, _capi.lib(), self.exposure_mode
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _capi.stream_ptr(dev)
         P, n_rows = len(off) - 1, off[-1]
         assert P >= 1 and off[0] == 0 and all(b > a for a, b in zip(off, off[1:])) and n_rows <= int(ev.shape[0])
         height, width = int(self.height), int(self.width)

@@ -6,16 +6,12 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._capi import check
+from ._capi import check, ptr, stream_ptr
 
 # aedat2_output.py:41-77
 _AEDAT2_LAYOUT = {(346, 260): (12, 22, 11, 1, 1), (240, 180): (12, 22, 11, 1, 1), (640, 480): (1, 11, 0, 1, 1)}
 
 logger = logging.getLogger(__name__)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
 
 
 _REC_DT = np.dtype([("max_events", "<i4"), ("flags", "<u4"), ("n_signal", "<u4"), ("n_events", "<u4"), ("n_on", "<u4"),
@@ -84,8 +80,8 @@ def _frame_recs(ev_offset, n_signal):
 
 
 def _format_text_call(ev, n, labels, recs, nrec, nsig0, out, scratch, stream):
-    check(_capi.lib().v2e_events_format_text(_ptr(ev) if n else None, n, recs, nrec, nsig0, 1 if labels else 0, _ptr(out),
-                                             int(out.numel()), _ptr(scratch), C.c_void_p(stream.cuda_stream)),
+    check(_capi.lib().v2e_events_format_text(ptr(ev) if n else None, n, recs, nrec, nsig0, 1 if labels else 0, ptr(out),
+                                             int(out.numel()), ptr(scratch), C.c_void_p(stream.cuda_stream)),
           "v2e_events_format_text")
 
 
@@ -103,7 +99,7 @@ def format_text(events_dev, labels=False, n_signal=None, frames=None, out=None):
     recs, nrec, nsig0 = None, 0, 0
     if labels and frames is not None:
         rec = torch.from_numpy(_frame_recs(*frames).view(np.uint8)).to(dev)
-        recs, nrec = _ptr(rec), len(frames[0])
+        recs, nrec = ptr(rec), len(frames[0])
     elif labels:
         nsig0 = n if n_signal is None else int(n_signal)
     own = out is None
@@ -126,8 +122,8 @@ def pack_aedat2(events_dev, width, height, noise_from=-1):
     xs, ys, ps, fx, fy = _AEDAT2_LAYOUT[(width, height)]
     n = int(events_dev.shape[0])
     out = torch.empty((n * 8,), dtype=torch.uint8, device=events_dev.device)
-    s = C.c_void_p(torch.cuda.current_stream(events_dev.device).cuda_stream)
-    check(_capi.lib().v2e_events_pack_aedat2(_ptr(events_dev.contiguous()), _ptr(out), n, width, height, xs, ys, ps, fx, fy,
+    s = stream_ptr(events_dev.device)
+    check(_capi.lib().v2e_events_pack_aedat2(ptr(events_dev.contiguous()), ptr(out), n, width, height, xs, ys, ps, fx, fy,
                                              int(noise_from), s), "v2e_events_pack_aedat2")
     return out
 
@@ -136,8 +132,8 @@ def pack_h5(events_dev):
     """events_dev: device float32 [N,4] -> device int64-free uint32 rows (as int32 tensor bit pattern) [N,4]."""
     n = int(events_dev.shape[0])
     out = torch.empty((n, 4), dtype=torch.int32, device=events_dev.device)  # torch has no uint32 arithmetic; same bits
-    s = C.c_void_p(torch.cuda.current_stream(events_dev.device).cuda_stream)
-    check(_capi.lib().v2e_events_pack_h5(_ptr(events_dev.contiguous()), _ptr(out), n, s), "v2e_events_pack_h5")
+    s = stream_ptr(events_dev.device)
+    check(_capi.lib().v2e_events_pack_h5(ptr(events_dev.contiguous()), ptr(out), n, s), "v2e_events_pack_h5")
     return out
 
 
@@ -156,6 +152,7 @@ class DeviceAEDat2Output:
         self.label_signal_noise = label_signal_noise
         self.numEventsWritten = self.numOnEvents = self.numOffEvents = 0
         self.file = open(filepath, 'wb')
+        self._staging = None
         self._writeHeader()
         atexit.register(self.cleanup)
 
@@ -234,15 +231,15 @@ class DeviceAEDat2Output:
             return
         ev = events_dev.contiguous()
         n = int(ev.shape[0])
-        st = self._staging = getattr(self, "_staging", None) or _Staging(ev.device)
+        st = self._staging = self._staging or _Staging(ev.device)
         xs, ys, ps, fx, fy = _AEDAT2_LAYOUT[(self.width, self.height)]
         with torch.cuda.stream(st.stream):
             recs, nrec = None, 0
             if self.label_signal_noise:
                 rec_t, nrec = st.frame_table(ev_offset, n_signal)
-                recs = _ptr(rec_t)
+                recs = ptr(rec_t)
             out = st.get("dev_bytes", 8 * n, torch.uint8)
-            check(_capi.lib().v2e_events_pack_aedat2_run(_ptr(ev), _ptr(out), n, self.width, self.height, xs, ys, ps, fx, fy, recs,
+            check(_capi.lib().v2e_events_pack_aedat2_run(ptr(ev), ptr(out), n, self.width, self.height, xs, ys, ps, fx, fy, recs,
                                                          nrec, C.c_void_p(st.stream.cuda_stream)), "v2e_events_pack_aedat2_run")
             on = (ev[:, 3] > 0).sum()
             host = st.to_host(out, 8 * n)
@@ -349,7 +346,7 @@ class DeviceTextOutput:
             recs, nrec = None, 0
             if frames is not None:
                 rec_t, nrec = st.frame_table(*frames)
-                recs = _ptr(rec_t)
+                recs = ptr(rec_t)
             scratch = st.get("scratch", int(_capi.lib().v2e_events_format_text_scratch_words(n)), torch.int64)
             total_h = st.get("total", 1, torch.int64, pinned=True)
             out = st.get("dev_bytes", 32 * n, torch.uint8)
@@ -436,9 +433,9 @@ class EventFrameAccumulator:
     def accumulate(self, events_dev, sensor_height=None, sensor_width=None):
         hr = self.histrange or [(0, sensor_height or self.height), (0, sensor_width or self.width)]  # renderer.py:232
         n = int(events_dev.shape[0])
-        s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        check(_capi.lib().v2e_events_accumulate_frame(_ptr(events_dev.contiguous()) if n else None, n, _ptr(self.currentFrame),
-                                                      _ptr(self._diff), self.height, self.width, float(hr[0][0]), float(hr[0][1]),
+        s = stream_ptr(self.device)
+        check(_capi.lib().v2e_events_accumulate_frame(ptr(events_dev.contiguous()) if n else None, n, ptr(self.currentFrame),
+                                                      ptr(self._diff), self.height, self.width, float(hr[0][0]), float(hr[0][1]),
                                                       float(hr[1][0]), float(hr[1][1]), self.full_scale_count, s),
               "v2e_events_accumulate_frame")
         return self.currentFrame

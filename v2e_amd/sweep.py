@@ -165,7 +165,7 @@ class ThresholdSweep(object):
                                       self.thresholds.ctypes.data_as(C.POINTER(C.c_double)),
                                       self.neg_thresholds.ctypes.data_as(C.POINTER(C.c_double)), T,
                                       (C.c_int * 4)(x0, x1, y0, y1), C.c_void_p(counts.data_ptr()), C.c_void_p(rule.data_ptr()),
-                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "v2e_thres_sweep")
+                                      _capi.stream_ptr(dev)), "v2e_thres_sweep")
             counts_h = counts.cpu().numpy()
             rule_on = rule.cpu().numpy() != 0
             on, off = counts_h[:, 0].copy(), counts_h[:, 1].copy()

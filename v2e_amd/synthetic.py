@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._capi import check
+from ._capi import check, ptr, stream_ptr
 from .emulator import default_event_capacity
 
 logger = logging.getLogger(__name__)
@@ -44,10 +44,6 @@ BACKGROUND = 127  # base_synthetic_input.BACKGROUND
 _NP_DT = {_capi.DT_U8: np.uint8, _capi.DT_F32: np.float32, _capi.DT_F64: np.float64}
 _TORCH_DT = {_capi.DT_U8: torch.uint8, _capi.DT_F32: torch.float32, _capi.DT_F64: torch.float64}
 _warned_host_video = False
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class _DeviceSource:
@@ -89,9 +85,6 @@ class _DeviceSource:
             raise ValueError("out must be a contiguous %s tensor [%d, %d, %d] on %s" % (dt, n, self.h, self.w, self.device))
         return f0, n, out
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _upload(self, a):
         return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
 
@@ -127,8 +120,8 @@ class _DotSource(_DeviceSource):
         base = dev.data_ptr()
         bg, fg, sigma, d, peak, low_cut, clip = self._dot_params()
         check(_capi.lib().v2e_synth_dots(C.c_void_p(base + no * 4), C.c_void_p(base + no * 4 + nd * 16), C.c_void_p(base), n, self.h,
-                                         self.w, _ptr(out), self.out_dtype, float(bg), float(fg), float(sigma), int(d), float(peak),
-                                         float(low_cut), int(clip), self._stream()), "v2e_synth_dots")
+                                         self.w, ptr(out), self.out_dtype, float(bg), float(fg), float(sigma), int(d), float(peak),
+                                         float(low_cut), int(clip), stream_ptr(self.device)), "v2e_synth_dots")
         dev.record_stream(torch.cuda.current_stream(self.device))
         return out, self.times[f0:f0 + n]
 
@@ -390,8 +383,8 @@ class gradients(_DeviceSource):
         f0, n, out = self._check_block(f0, n, out)
         low, high, diff, w2 = self.constants()
         p = self._upload(np.asarray(self.bump_centres(f0, n), np.float64))
-        check(_capi.lib().v2e_synth_gradients(_ptr(p), n, self.h, self.w, _ptr(out), float(low), float(high), float(-diff / w2),
-                                              float(w2), self._stream()), "v2e_synth_gradients")
+        check(_capi.lib().v2e_synth_gradients(ptr(p), n, self.h, self.w, ptr(out), float(low), float(high), float(-diff / w2),
+                                              float(w2), stream_ptr(self.device)), "v2e_synth_gradients")
         p.record_stream(torch.cuda.current_stream(self.device))
         return out, self.times[f0:f0 + n]
 
@@ -450,9 +443,9 @@ class barberpole(_DeviceSource):
         f0, n, out = self._check_block(f0, n, out)
         wavelength, low, diff, tan = self.constants()
         t = self._upload(np.asarray(self.times[f0:f0 + n], np.float64))
-        check(_capi.lib().v2e_synth_barberpole(_ptr(t), n, self.h, self.w, _ptr(out), float(low), float(diff), float(tan),
+        check(_capi.lib().v2e_synth_barberpole(ptr(t), n, self.h, self.w, ptr(out), float(low), float(diff), float(tan),
                                                float(self.speed_pps), float(2 * np.pi), float(wavelength), int(self.minx),
-                                               int(self.maxx), int(self.miny), int(self.maxy), int(self.bg), self._stream()),
+                                               int(self.maxx), int(self.miny), int(self.maxy), int(self.bg), stream_ptr(self.device)),
               "v2e_synth_barberpole")
         t.record_stream(torch.cuda.current_stream(self.device))
         return out, self.times[f0:f0 + n]
@@ -467,6 +460,7 @@ class SyntheticToEvents:
         if int(block_frames) < 1:
             raise ValueError("block_frames must be positive")
         self.source, self.emu, self.block_frames = source, emulator, int(block_frames)
+        self._side = None  # run(): the stream the source renders on, created on first need
 
     def run(self, on_events=None, return_device=False):
         """Returns (events, counts per frame, n_frames).  on_events(events, counts, frame0) is called once per block in frame order
@@ -482,9 +476,9 @@ class SyntheticToEvents:
         N, B = src.total_frames(), self.block_frames
         H, W, dev = src.h, src.w, src.device
         main = torch.cuda.current_stream(dev)
-        side = self.__dict__.get("_side")
-        if side is None:
-            side = self._side = torch.cuda.Stream(dev)
+        if self._side is None:
+            self._side = torch.cuda.Stream(dev)
+        side = self._side
         side.wait_stream(main)
         blocks = [(f0, min(B, N - f0)) for f0 in range(0, N, B)]
         with torch.cuda.stream(side):

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._capi import check
+from ._capi import check, ptr, stream_ptr
 
 REPRESENTATIONS = ("count", "voxel", "time_surface")
 MAX_RUN_WINDOWS = 1 << 22  # windows one run may touch before add_run refuses (a time stamp far from the others)
@@ -79,10 +79,6 @@ def plan_windows(t_end, k_open=0, window_s=None, t_start=0.0, bounds=None, voxel
         per = n_complete if voxel_plane_bytes <= 0 else max(1, int(max_scratch_bytes) // int(voxel_plane_bytes))
         blocks = [(a, min(a + per, n_complete)) for a in range(0, n_complete, per)]
     return n_complete, has_open, blocks
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class EventTensorizer(object):
@@ -151,9 +147,6 @@ class EventTensorizer(object):
             raise ValueError("out[%r] must be a contiguous %s device tensor [>= %d, %d, %d, %d]" % ((rep, self._DTYPES[rep], n) + shape))
         return o[:n]
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _run_t_end(self, events, n, counts, frame0, t_end):
         if t_end is not None:
             return float(t_end)
@@ -185,7 +178,7 @@ class EventTensorizer(object):
         nc, has_open, blocks = plan_windows(t_end, self.k_open, self.window_s, self.t_start, self.bounds,
                                             8 * B * H * W if voxel else 0, self.max_scratch_bytes)
         self._t_end = max(self._t_end, t_end)
-        lib, stream, first = _capi.lib(), self._stream(), self.k_open
+        lib, stream, first = _capi.lib(), stream_ptr(self.device), self.k_open
         res = {"windows": (first, nc)}
         for rep in self.representations:
             res[rep] = self._output(rep, nc, out)
@@ -193,7 +186,7 @@ class EventTensorizer(object):
         if nc:
             for rep, carry in (("count", self._count_open), ("time_surface", self._surf_open)):
                 if carry is not None:
-                    check(lib.v2e_tensorize_move_zero(_ptr(res[rep]), nc * pw, _ptr(carry), pw, stream), "v2e_tensorize_move_zero")
+                    check(lib.v2e_tensorize_move_zero(ptr(res[rep]), nc * pw, ptr(carry), pw, stream), "v2e_tensorize_move_zero")
         acc = None
         if voxel and blocks:
             acc = torch.empty((max(b - a for a, b in blocks), B, H, W), dtype=torch.int64, device=self.device)
@@ -201,17 +194,17 @@ class EventTensorizer(object):
 
         def scatter(nk, open_, block, all_reps):
             a, b = block
-            check(lib.v2e_tensorize_scatter(_ptr(events) if n else None, n, H, W, self.t_start, self.window_s or 0.0, bounds_ptr, first,
-                                            nk, open_, _ptr(res.get("count")) if all_reps and nc else None,
-                                            _ptr(self._count_open) if all_reps else None, _ptr(acc) if b > a else None,
-                                            _ptr(self._voxel_open), a, b, B, _ptr(res.get("time_surface")) if all_reps and nc else None,
-                                            _ptr(self._surf_open) if all_reps else None, _ptr(self._counters) if all_reps else None,
+            check(lib.v2e_tensorize_scatter(ptr(events) if n else None, n, H, W, self.t_start, self.window_s or 0.0, bounds_ptr, first,
+                                            nk, open_, ptr(res.get("count")) if all_reps and nc else None,
+                                            ptr(self._count_open) if all_reps else None, ptr(acc) if b > a else None,
+                                            ptr(self._voxel_open), a, b, B, ptr(res.get("time_surface")) if all_reps and nc else None,
+                                            ptr(self._surf_open) if all_reps else None, ptr(self._counters) if all_reps else None,
                                             stream), "v2e_tensorize_scatter")
             self.scatter_launches += 1 if n else 0
 
         def voxel_block(a, b):
             vw = 2 * B * H * W  # 32-bit words of an int64 voxel plane
-            check(lib.v2e_tensorize_move_zero(_ptr(acc), (b - a) * vw, _ptr(self._voxel_open) if a == 0 else None, vw if a == 0 else 0,
+            check(lib.v2e_tensorize_move_zero(ptr(acc), (b - a) * vw, ptr(self._voxel_open) if a == 0 else None, vw if a == 0 else 0,
                                               stream), "v2e_tensorize_move_zero")
 
         # the first launch feeds every representation, the open window and the counters; the voxel blocks after the first re-read
@@ -225,10 +218,10 @@ class EventTensorizer(object):
                 if i:
                     voxel_block(a, b)
                     scatter(nc, 0, (a, b), False)
-                check(lib.v2e_tensorize_voxel_finish(_ptr(acc), (b - a) * B * H * W, _ptr(res["voxel"][a:b]), 0, stream),
+                check(lib.v2e_tensorize_voxel_finish(ptr(acc), (b - a) * B * H * W, ptr(res["voxel"][a:b]), 0, stream),
                       "v2e_tensorize_voxel_finish")
         if nc and self._surf_state is not None:
-            check(lib.v2e_tensorize_surface_finish(_ptr(res["time_surface"]), nc, pw, _ptr(self._surf_state), stream),
+            check(lib.v2e_tensorize_surface_finish(ptr(res["time_surface"]), nc, pw, ptr(self._surf_state), stream),
                   "v2e_tensorize_surface_finish")
         self.k_open = first + nc
         return res
@@ -236,7 +229,7 @@ class EventTensorizer(object):
     def flush(self, out=None):
         """The open window as the clip's final, partial one: {"windows": (index, 1), <representation>: [1, ...]}; the next window
         is open afterwards.  With an explicit table that is used up: (K, 0) and empty tensors."""
-        lib, stream, first = _capi.lib(), self._stream(), self.k_open
+        lib, stream, first = _capi.lib(), stream_ptr(self.device), self.k_open
         n = 0 if self.bounds is not None and first >= len(self.bounds) - 1 else 1
         res = {"windows": (first, n)}
         for rep in self.representations:
@@ -247,12 +240,12 @@ class EventTensorizer(object):
         pw = 2 * H * W
         for rep, carry in (("count", self._count_open), ("time_surface", self._surf_open)):
             if carry is not None:
-                check(lib.v2e_tensorize_move_zero(_ptr(res[rep]), pw, _ptr(carry), pw, stream), "v2e_tensorize_move_zero")
+                check(lib.v2e_tensorize_move_zero(ptr(res[rep]), pw, ptr(carry), pw, stream), "v2e_tensorize_move_zero")
         if self._voxel_open is not None:
-            check(lib.v2e_tensorize_voxel_finish(_ptr(self._voxel_open), B * H * W, _ptr(res["voxel"]), 1, stream),
+            check(lib.v2e_tensorize_voxel_finish(ptr(self._voxel_open), B * H * W, ptr(res["voxel"]), 1, stream),
                   "v2e_tensorize_voxel_finish")
         if self._surf_state is not None:
-            check(lib.v2e_tensorize_surface_finish(_ptr(res["time_surface"]), 1, pw, _ptr(self._surf_state), stream),
+            check(lib.v2e_tensorize_surface_finish(ptr(res["time_surface"]), 1, pw, ptr(self._surf_state), stream),
                   "v2e_tensorize_surface_finish")
         self.k_open = first + 1
         return res
