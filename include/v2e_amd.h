@@ -704,6 +704,36 @@ int v2e_denoise_ages(const float *events, int64_t n, int H, int W, const int64_t
 int v2e_denoise_map_update(const float *events, const int64_t *sorted_keys, const int32_t *seg, int H, int W, float *last_t,
                            void *stream);
 
+/* Per-event time-surface patches: for every row of a device-resident run the (2r+1) x (2r+1) patch of ages and polarities around
+ * it, as the maps were just before the row (v2e_amd/csrc/patches.hip; host side v2e_amd/patches.py, EventPatches).
+ * Rows and validity: rows are events[n][4] = (t, x = column, y = row, p), taken in row order.  A row is bad under exactly
+ * DenoiseSweep's rule: t not finite, or x / y not an integer value inside [0,W) / [0,H); p is not examined for validity.  A bad row
+ * reads and writes no map and gets valid = 0; its features are the "none" values below.
+ * Carried maps: last_t is float32 [H][W] and starts at -inf; last_p is int8 [H][W] and starts at 0; both are carried on the device
+ * from call to call.
+ * Per-row patch: for a valid row i at (x, y) and every offset (dy, dx) in [-r, r]^2, r = 1, 2 or 3, the centre included, the patch
+ * index is [dy + r][dx + r].  Let q = (x + dx, y + dy).  If q is outside the sensor the entry is none.  Otherwise T_q and P_q are
+ * taken from the latest valid row j < i at q in this call: T_q is its t, P_q the sign of its p (+1 if p > 0, else -1).  If no such
+ * row exists in this call, the carried maps supply T_q and P_q; a carried T_q of -inf means none.  age = (double)t_i - (double)T_q;
+ * a T_q later than t_i gives a negative age, which is kept.  The centre entry is the previous event at the same pixel: the row is
+ * never in its own patch.
+ * After reading, the row stamps last_t[y][x] = t_i and last_p[y][x] = sign(p_i).
+ * Output: out is float32 [n][2][P][P], P = 2r + 1.  mode 0 ("age"): channel 0 is (float)age, rounded to nearest even, +inf where
+ * none; channel 1 is P_q as +-1.0, 0 where none.  mode 1 ("linear", tau > 0 finite): channel 0 is 0 where none or age >= tau, 1
+ * where age <= 0, otherwise (float)(1 - age / tau), the division and the subtraction each rounded in float64; channel 1 is P_q
+ * where channel 0's entry is not of the first kind, that is, not none and age < tau, otherwise 0.
+ * Invariance: the result depends on the row order alone; a clip cut into several calls, or a call cut into passes, gives identical
+ * features and identical final maps.
+ * One pass (n <= 2^31 - 1 rows, H * W <= 2^31 - 1) is v2e_denoise_keys, a sort of the keys, v2e_denoise_segments, then:
+ * v2e_patches_features: writes EVERY element of out[n][2][P][P] and valid[n] (uint8), bad rows included, whatever the buffers held;
+ * the maps are only read.  Per entry one binary search of q's stretch of the sorted keys for the largest row index below i and one
+ * 16-byte gather of that row.  Element offsets into out are 64-bit.  events must be 16-byte aligned.
+ * v2e_patches_map_update: last_t[p], last_p[p] from pixel p's last row of the pass; behind v2e_patches_features on the same stream. */
+int v2e_patches_features(const float *events, int64_t n, int H, int W, const int64_t *sorted_keys, const int32_t *seg, const float *last_t,
+                         const int8_t *last_p, int radius, int mode, double tau, float *out, uint8_t *valid, void *stream);
+int v2e_patches_map_update(const float *events, const int64_t *sorted_keys, const int32_t *seg, int H, int W, float *last_t, int8_t *last_p,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

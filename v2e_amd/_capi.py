@@ -194,6 +194,8 @@ SIGNATURES = {
     "v2e_denoise_segments": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp]),
     "v2e_denoise_ages": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _i, _d, _vp]),
     "v2e_denoise_map_update": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "v2e_patches_features": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp]),
+    "v2e_patches_map_update": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
 }
 
 # dev entry points the library exports outside include/v2e_amd.h: typed by lib() when present, never required

@@ -15,24 +15,13 @@
 // independent of the others, every sum is an integer atomic (LDS int32 per workgroup, flushed with 64-bit global atomics), and
 // the result does not depend on how threads are scheduled or how a clip is cut into calls.
 #include "common.h"
+#include "rowkeys.h"
 
 namespace {
 
 constexpr int MAX_TAUS = 256;
 constexpr int LDS_LABEL_BOUNDS_MAX = 2048;                  // label bounds staged in LDS up to this many entries (16 KB)
-constexpr long long KEY_BAD = 0x7fffffffffffffffLL;         // sorts behind every valid key as a signed 64-bit value
-constexpr int AGES_MAX_BLOCKS = 2048;
-
-// the pixel of a valid row, -1 for a bad one (the float comparisons come first: they refuse NaN and everything the int
-// conversion cannot hold)
-__device__ __forceinline__ long long row_pixel(const float4 e, int H, int W)
-{
-    const int x = (int)e.y, y = (int)e.z;
-    if (!(e.y >= 0.0f && e.y < (float)W && e.z >= 0.0f && e.z < (float)H && (float)x == e.y && (float)y == e.z &&
-          fabsf(e.x) <= 3.402823466e+38f))
-        return -1;
-    return (long long)y * W + x;
-}
+constexpr int AGES_MAX_BLOCKS = 2048;                       // (KEY_BAD and row_pixel: rowkeys.h)
 
 __global__ __launch_bounds__(256) void k_denoise_keys(const float4 *__restrict__ ev, long long n, int H, int W, long long *__restrict__ keys,
                                                       unsigned char *__restrict__ keep)
