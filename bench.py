@@ -20,14 +20,16 @@ compared output for output.
 
 N > 1 (driver: python -m torch.distributed.run ...): one independent clip per GPU
 (BASELINE.json configs[4]); every step ends with an RCCL all-gather of the ranks' event
-streams, overlapped with the next step's kernels on a side stream.  The line then also
-carries `compute_only` (the same loop without the exchange) and `bytes_gathered`.
+streams, overlapped with the next step's kernels on a side stream; the line then also
+carries `with_allgather` (the bytes gathered per rank and step, the wire format).
 
-Extra objects on the JSON line: roofline (dominant emulator kernel, HIP-event timed),
-cpu_baseline (CPU oracle on this host, rank 0, N=1; + the recorded reference torch-CPU run),
-frame_api / delivered_to_host (what a v2e.py caller of the drop-in class gets), slomo
-(interpolated frames/s of the SuperSloMo HIP path with its own MFMA roofline), batched,
-hd_noisy, end_to_end.
+A plain run does what the headline needs and no more: set-up, warm-up, the timed steps, --dump-outputs, the line (its `roofline`
+holds `whole_step` alone: arithmetic on the headline's own time).  --full adds every measurement that takes a run of its own:
+roofline (dominant emulator kernel, stamped on the device and HIP-event timed in re-runs of the loop), cpu_baseline (CPU oracle
+on this host, rank 0, N=1; + the recorded reference torch-CPU run), frame_api / delivered_to_host (what a v2e.py caller of the
+drop-in class gets), slomo (interpolated frames/s of the SuperSloMo HIP path with its own MFMA roofline) in its three conv
+arithmetics and at the HD size, batched, hd_noisy, end_to_end, self_allgather; with N > 1 `compute_only` (the same loop without
+the exchange) and slomo_sharded.  --no-cpu-baseline, --no-extras and --no-roofline-rerun take their parts out of a --full run.
 """
 import argparse
 import json
@@ -440,16 +442,24 @@ def main():
                          % MIN_BLOCK_STEPS)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the last step's event rows and per-frame counts to DIR/*.npy")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the slomo / batched / frame-API side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the headline, every measurement that takes a run of its own: the chain kernel's roofline re-runs, the "
+                         "slomo / batched / frame-API side measurements, the CPU baseline, with N > 1 the loop without the exchange")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle's run")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the slomo / batched / frame-API side measurements")
     ap.add_argument("--no-allgather", action="store_true")
     ap.add_argument("--force-allgather", action="store_true", help="run the RCCL gather path even with one rank (self-test)")
     ap.add_argument("--gather-algo", choices=["allgather", "p2p"], default="allgather",
                     help="event-stream exchange: ncclAllGather on padded payloads, or grouped point-to-point sends of exact sizes")
     ap.add_argument("--gather-wire", choices=["auto", "pack32", "pack64"], default="auto")
     ap.add_argument("--no-roofline-rerun", action="store_true",
-                    help="skip the instrumented re-run behind the timed blocks (profiling: the trace then holds the timed configuration's launches only)")
+                    help="with --full: skip the instrumented re-run behind the timed blocks (profiling: the trace then holds the timed "
+                         "configuration's launches only)")
     args = ap.parse_args()
+    # what a run measures behind its headline: nothing unless --full asks, and then all but what the --no-... options take out
+    roofline_rerun = args.full and not args.no_roofline_rerun
+    extras = args.full and not args.no_extras
+    cpu_oracle = args.full and not args.no_cpu_baseline
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args.gpus, sys.argv[1:])  # does not return
@@ -537,7 +547,7 @@ def main():
     if args.dump_outputs and rank == 0:
         dumped = dump_outputs(args.dump_outputs, *timed.pending.result())
     compute_only = None
-    if use_gather:  # the same loop without the exchange: how much of the N-GPU number the interconnect decides
+    if use_gather and args.full:  # the same loop without the exchange: how much of the N-GPU number the interconnect decides
         emu_c = make_emu()
         compute_only = median_block(timed_blocks(emu_c, None))
 
@@ -572,6 +582,7 @@ def main():
             out["compute_only"] = {"value": round(compute_only[1] / compute_only[0] / 1e6, 3), "unit": "Mevents/s",
                                    "ms_per_step": round(compute_only[0] / compute_only[2] * 1e3, 4),
                                    "note": "same loop, no event-stream exchange"}
+        if use_gather:
             out["with_allgather"] = {"value": out["value"], "unit": "Mevents/s",
                                      "bytes_gathered_per_rank_per_step": int(gather.bytes_gathered / max(K + Wm, 1)),
                                      "algo": args.gather_algo,
@@ -579,13 +590,13 @@ def main():
                                                      if gather.wire == "pack32" else "8 B per event (v2e_events_pack64)")}
 
     # ---------------- roofline of the dominant emulator kernel (rank 0, HIP events, same workload)
-    if rank == 0 and not STUB and args.no_roofline_rerun:
+    if rank == 0 and not STUB and not roofline_rerun:
         whole = emulator_bytes_per_pixel(DEFAULT_KW) * H * W + 16 * tot_events / (world * Km * F)
         out["roofline"] = {"bound": "hbm", "kernel": "k_chain", "achieved": None, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": None, "traffic": None,
                            "whole_step": {"algorithmic_bytes_per_frame": int(whole), "achieved_GBps": round(whole * Km * F / elapsed / 1e9, 2),
                                           "frac": round(whole * Km * F / elapsed / HBM_PEAK, 5)},
-                           "note": "--no-roofline-rerun: no per-launch measurement in this run"}
-    if rank == 0 and not STUB and not args.no_roofline_rerun:
+                           "note": "no per-launch measurement in this run: --full (without --no-roofline-rerun) takes one"}
+    if rank == 0 and not STUB and roofline_rerun:
         eng = emu._engine
         P = emu._params()
         buf = torch.empty((F, H, W), dtype=torch.uint8, device=device)
@@ -711,7 +722,7 @@ def main():
                     "algorithmic bytes: HBM is not what binds this kernel -- instruction_issue states the fraction of the resource that "
                     "does, and whole_step prices the complete frame (state + event rows) against the driver-timed region",
         }
-        if not args.no_extras and world == 1:
+        if extras and world == 1:
             try:
                 from v2e_amd.benchutil import batched_emulator_bench, e2e_bench, hd_noisy_emulator_bench, slomo_bench
 
@@ -749,11 +760,11 @@ def main():
                     out["self_allgather"] = self_allgather_bench(device, frames_all)
                 except Exception as e:
                     out["self_allgather"] = {"error": repr(e)[:300]}
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if rank == 0 and cpu_oracle and world == 1:
         # (behind the GPU legs: its 64 host threads leave the main thread on whatever NUMA node the scheduler likes, and pinned host
         #  buffers allocated from there cost the PCIe legs half their rate -- delivered_to_host 1.0 instead of 3.1 Gev/s, round 6)
         out["cpu_baseline"] = cpu_baseline(frames_all[:1501].cpu().numpy())
-    if dist is not None and not args.no_extras:
+    if dist is not None and extras:
         # the SuperSloMo stage of ONE clip sharded over the ranks by source pairs (every rank takes part; rank 0 reports); stub mode:
         # the same collective sequence over gloo with a stand-in for the interpolator, a small clip
         try:

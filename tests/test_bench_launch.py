@@ -28,14 +28,24 @@ def _one_json_line(stdout):
     return json.loads(lines[0])
 
 
-def _check_line(d, n, steps, warmup):
+PLAIN = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
+FULL_ONLY = ("compute_only", "slomo_sharded", "cpu_baseline", "frame_api", "delivered_to_host", "batched", "hd_noisy", "slomo",
+             "slomo_f32", "slomo_bf16x3", "slomo_hd", "end_to_end", "self_allgather")
+
+
+def _check_line(d, n, steps, warmup, full=True):
     assert d["n_gpus"] == n and d["ranks_seen"] == n and d["steps"] == steps and d["warmup"] == warmup
     assert d["data"] == "stub" and d["metric"].startswith("STUB"), "a stub run must never look like a measurement"
     assert d["scaling"] == "weak" and d["higher_is_better"] is True and d["vs_baseline"] is None
     assert d["value"] > 0 and d["ms_per_step"] > 0
+    assert all(k in d for k in PLAIN) and d["unit"] == "Mevents/s" and d["dtype"] == "f64"
+    if not full:  # a plain run: the headline and nothing that takes a run of its own
+        assert not [k for k in FULL_ONLY if k in d]
     if n > 1:
         assert d["config"]["event_stream_allgather"] is True
-        assert d["compute_only"]["value"] > 0 and d["with_allgather"]["bytes_gathered_per_rank_per_step"] > 0
+        assert d["with_allgather"]["bytes_gathered_per_rank_per_step"] > 0
+    if n > 1 and full:
+        assert d["compute_only"]["value"] > 0
         # the SuperSloMo stage of one clip sharded over the ranks by source pairs: every rank went through the leg's collectives in
         # the same order (no hang), and rank 0 assembled the unsharded clip (the stub interpolator's frames, compared in the leg)
         sh = d["slomo_sharded"]
@@ -52,8 +62,9 @@ def _check_line(d, n, steps, warmup):
 
 @pytest.mark.parametrize("n", [2, 4])
 def test_bare_bench_py_self_launches_ranks(n):
-    """`python bench.py --gpus N` exactly as BENCH_r04.json's cmd was formed, with N > 1 and no launcher around it."""
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", str(n), "--steps", "3", "--warmup", "1", "--blocks", "2"],
+    """`python bench.py --gpus N` as BENCH_r04.json's cmd was formed, with N > 1 and no launcher around it; --full: the loop without
+    the exchange and the sharded SloMo leg behind the headline."""
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", str(n), "--steps", "3", "--warmup", "1", "--blocks", "2", "--full"],
                        cwd=ROOT, env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     _check_line(_one_json_line(p.stdout.decode()), n, 3, 1)
@@ -68,7 +79,7 @@ def test_bench_py_under_torch_distributed_run():
     s.close()
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--blocks", "1"], cwd=ROOT, env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        "--blocks", "1", "--full"], cwd=ROOT, env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     d = [json.loads(ln) for ln in p.stdout.decode().splitlines() if ln.strip().startswith("{")]
     assert len(d) == 1  # rank 0 only
@@ -80,8 +91,28 @@ def test_bare_bench_py_single_rank_stub():
                        cwd=ROOT, env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     d = _one_json_line(p.stdout.decode())
-    _check_line(d, 1, 2, 1)
+    _check_line(d, 1, 2, 1, full=False)
     assert d["collective_backend"] is None
+
+
+def test_plain_run_of_two_ranks_measures_the_headline_alone():
+    """Without --full the N > 1 line carries the headline with the exchange on and what it gathered, and neither the loop without
+    the exchange nor the sharded SloMo leg has run."""
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--blocks", "2"],
+                       cwd=ROOT, env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    _check_line(_one_json_line(p.stdout.decode()), 2, 3, 1, full=False)
+
+
+def test_full_single_rank_stub_adds_the_cpu_baseline():
+    """--full at N = 1 in stub mode: the CPU oracle's leg runs behind the headline, over the stub's 13 frames of 4x6 (the GPU legs
+    need a device)."""
+    p = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--blocks", "1", "--full"],
+                       cwd=ROOT, env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    d = _one_json_line(p.stdout.decode())
+    _check_line(d, 1, 2, 1)
+    assert d["cpu_baseline"]["value"] >= 0 and d["cpu_baseline"]["cores"] == 1
 
 
 def test_world_size_mismatch_is_an_error():
