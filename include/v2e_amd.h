@@ -669,9 +669,29 @@ typedef struct v2e_sweep_params {
 int v2e_thres_sweep(const void *frames, int frame_dtype, int F, int H, int W, const double *t_frames, const v2e_sweep_params *p,
                     const double *pos, const double *neg, int T, const int roi[4], uint64_t *counts_dev, int32_t *rule_on_dev,
                     void *stream);
+/* v2e_thres_sweep_chunk: the same sweep for a clip that arrives in chunks: the call runs v2e_thres_sweep's per-frame arithmetic
+ * over the F >= 1 frames of one chunk, whose first frame is the clip's frame frame0, and carries every column's state from call to
+ * call in device planes of the caller's: lp [H*W] of R (the same for every column) and base [T][H*W] of R, R = double when
+ * cutoff_hz > 0 and float otherwise.  The state at the start of the chunk is read from lp_in / base_in and the state behind its
+ * last frame is written to lp_out / base_out, which must be other planes: the kernel never writes what it reads, so the state at
+ * the start of the chunk is still there when the chunk's flags are known.  frame0 == 0: frames[0] is the clip's first frame, which
+ * initialises the state and emits nothing; lp_in / base_in are not read (and may be null) and t_previous must be 0.  frame0 > 0:
+ * every frame is an ordinary one, and t_previous is the emulator's t_previous when it is given frames[0]: the time of the clip's
+ * frame frame0 - 1, except that it is 0 for frame0 == 1 (the first frame does not advance it, emulator.py:717); t_frames[0] must
+ * lie after it.  The Philox keys use the clip's frame index frame0 + f, whichever half of a frame pair the chunk begins on.
+ * counts_dev is ADDED to and rule_on_dev OR-ed into -- zero both before the clip's first chunk -- so that after the last chunk they
+ * hold what v2e_thres_sweep gives for the whole clip, bit for bit, in every column whose flag is 0.  A pixel's own 32-bit ON / OFF
+ * total is per chunk.  Same model parameters, thresholds and ROI in every call of a clip; everything else as for v2e_thres_sweep
+ * (V2E_EINVAL also for F < 1, frame0 < 0 or frame0 + F >= 2^31, a null or aliased state plane). */
+int v2e_thres_sweep_chunk(const void *frames, int frame_dtype, int F, int H, int W, const double *t_frames, int64_t frame0,
+                          double t_previous, const v2e_sweep_params *p, const double *pos, const double *neg, int T, const int roi[4],
+                          const void *lp_in, const void *base_in, void *lp_out, void *base_out, uint64_t *counts_dev,
+                          int32_t *rule_on_dev, void *stream);
 /* v2e_thres_sweep_info: the kernel a sweep with this state type / kind of thresholds / cols_per_thread runs: the columns per
  * thread in force, its vector registers per lane, and how many of its 256-thread workgroups a CU holds.  Outputs may be null. */
 int v2e_thres_sweep_info(int f64_state, int scalar_thres, int cols_per_thread, int *cols_out, int *vgprs, int *workgroups_per_cu);
+/* v2e_thres_sweep_chunk_info: the same of the kernel v2e_thres_sweep_chunk runs (the instantiation that carries the state). */
+int v2e_thres_sweep_chunk_info(int f64_state, int scalar_thres, int cols_per_thread, int *cols_out, int *vgprs, int *workgroups_per_cu);
 
 /* The spatio-temporal correlation filter (STCF; with one supporting neighbour jAER's BackgroundActivityFilter) scored for every
  * (k, tau) in one pass over the rows of a device-resident run (v2e_amd/csrc/denoise.hip; host side v2e_amd/denoise.py,

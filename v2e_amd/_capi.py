@@ -190,6 +190,9 @@ SIGNATURES = {
     "v2e_thres_sweep": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_d), C.POINTER(SweepParams), C.POINTER(_d), C.POINTER(_d), _i,
                              C.POINTER(_i), _vp, _vp, _vp]),
     "v2e_thres_sweep_info": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "v2e_thres_sweep_chunk": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_d), _i64, _d, C.POINTER(SweepParams), C.POINTER(_d), C.POINTER(_d), _i,
+                                   C.POINTER(_i), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "v2e_thres_sweep_chunk_info": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "v2e_denoise_keys": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp]),
     "v2e_denoise_segments": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp]),
     "v2e_denoise_ages": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _i, _d, _vp]),

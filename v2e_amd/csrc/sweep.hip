@@ -18,6 +18,14 @@
 // so every column runs as if the rule were off and raises a sticky flag as soon as a pixel's count reaches the frame's
 // FrameCtl::refr_on_n (the smallest M for which the rule is on).  A column whose flag stays 0 is exact; the others are the
 // caller's to recompute with the emulator itself.
+//
+// A clip may arrive in chunks (v2e_thres_sweep_chunk): the same kernel template with CARRY = true takes lp and every column's base
+// from planes of the caller's, [npx] and [T][npx] of R (a wave's 64 pixels of a column are 64 consecutive values: one coalesced
+// load and store per column and thread, no LDS), and leaves the state behind the chunk's last frame in a second set of planes.  It
+// never writes what it reads: when a flag rises in a chunk, the state at the START of that chunk -- exact by the invariant above --
+// is still there for the emulator that takes the column over.  Counts are added to, flags OR-ed into, Philox is keyed by the
+// clip's frame index.  Registers, occupancy and time of the CARRY = false instantiations are those the kernel had before it had
+// the parameter (profiles/r18_sweep_stream.txt).
 #include "common.h"
 #include "../../include/v2e_detmath.h"
 #include "emu_shared.h"
@@ -49,8 +57,22 @@ struct SweepArgs {
     int *rule_on;               // [T]
 };
 
-template <typename R, int TB, bool SCALAR>
-__global__ __launch_bounds__(BLOCK) void k_sweep(SweepArgs a)
+// What a chunk of a streamed clip adds (v2e_thres_sweep_chunk): the clip's index of the chunk's first frame and the per-column state
+// carried from call to call.  The kernel never writes what it reads: the state at the start of the chunk outlives the chunk.
+struct SweepCarry {
+    uint32_t frame0 = 0u;     // the clip's index of frames[0]; 0: that frame initialises the state and the in-planes are not read
+    const void *lp_in = nullptr;   // [npx] of R
+    const void *base_in = nullptr; // [T][npx] of R: column j's plane is 64 consecutive values to a wave
+    void *lp_out = nullptr, *base_out = nullptr;
+};
+
+// One pixel through the F frames for TB columns.  CARRY = false is the whole clip (v2e_thres_sweep; cy is not read); CARRY = true
+// is one chunk of it (v2e_thres_sweep_chunk): the state comes from and goes to SweepCarry's planes, the Philox keys use the clip's
+// frame index frame0 + f, and a pixel's 32-bit ON / OFF registers hold the chunk's events only.  (One kernel template, not a body
+// shared by two kernels: inlined from a function, the 16-column instantiations of the whole-clip kernel took 14 to 22 more
+// registers; as a template parameter they keep the registers and occupancy they had without it, profiles/r18_sweep_stream.txt.)
+template <typename R, int TB, bool SCALAR, bool CARRY>
+__global__ __launch_bounds__(BLOCK) void k_sweep(SweepArgs a, SweepCarry cy)
 {
     static_assert(TB >= 1 && TB <= 32, "one flag bit per column of the chunk");
     __shared__ float s_lutL[256];
@@ -106,9 +128,12 @@ __global__ __launch_bounds__(BLOCK) void k_sweep(SweepArgs a)
     }
     constexpr double QMAX = sizeof(R) == 8 ? 1.0e9 : 1.0e6; // quotients beyond it (and NaN) take the generic path
 
-    // ---- the first frame initialises the state and emits nothing (k_init)
+    // ---- the clip's first frame initialises the state and emits nothing (k_init); a later chunk takes up the carried state
+    const bool first = !CARRY || cy.frame0 == 0u;
+    const uint32_t g0 = CARRY ? cy.frame0 : 0u; // the emulator's frame index of frames[0]: the clip's first frame is 0, clip 0
+    const int fs = first ? 1 : 0;               // the first frame that is an ordinary one
     R lp;
-    {
+    if (first) {
         const int px = valid ? (int)fp[0] : 0;
         const double L = (double)s_lutL[px];
         if (a.has_cutoff) {
@@ -118,21 +143,29 @@ __global__ __launch_bounds__(BLOCK) void k_sweep(SweepArgs a)
         } else {
             lp = (R)L;
         }
+    } else {
+        lp = ((const R *)cy.lp_in)[valid ? p : 0];
     }
     R b[TB];
     uint32_t n_on[TB], n_off[TB];
 #pragma unroll
     for (int c = 0; c < TB; ++c) { b[c] = lp; n_on[c] = 0u; n_off[c] = 0u; }
+    if (CARRY && !first) {
+#pragma unroll
+        for (int c = 0; c < TB; ++c) b[c] = ((const R *)cy.base_in)[(size_t)min(j0 + c, a.T - 1) * a.npx + (valid ? p : 0)];
+    }
     uint32_t flags = 0u; // bit c: the refractory rule would have switched on in column j0 + c
 
-    float r_odd = 0.f, u_odd = 0.f, r_even = 0.f, u_even = 0.f; // the draws of the current frame pair
+    // the draws of the current frame pair: made at the pair's first half, and at the first frame whichever half it is (a chunk may
+    // begin on the second)
+    float r_odd = 0.f, u_odd = 0.f, r_even = 0.f, u_even = 0.f;
     bool have_pair = false;
-    int px_next = (valid && a.F > 1) ? (int)fp[(size_t)a.npx] : 0;
-    for (int f = 1; f < a.F; ++f) {
+    int px_next = (valid && a.F > fs) ? (int)fp[(size_t)fs * a.npx] : 0;
+    for (int f = fs; f < a.F; ++f) {
         const int px = px_next;
         if (valid && f + 1 < a.F) px_next = (int)fp[(size_t)(f + 1) * a.npx]; // (in flight while this frame is computed)
         const SweepFrame sf = a.tab[f];
-        const uint32_t gf = (uint32_t)f; // the emulator's frame index: the first frame is 0, clip 0
+        const uint32_t gf = g0 + (uint32_t)f;
         if (a.need_r) {                  // one Philox call per pair of frames (v2e_detmath.h)
             if (!have_pair || v2e_frame_half(gf) == 0u)
                 v2e_draw_pair(a.seed, 0u, v2e_frame_pair(gf), (uint32_t)p, 1, &r_odd, &u_odd, &r_even, &u_even);
@@ -184,6 +217,12 @@ __global__ __launch_bounds__(BLOCK) void k_sweep(SweepArgs a)
         }
     }
     if (!valid) flags = 0u;
+    if (CARRY && valid) { // the state for the next chunk (lp is the same in every chunk of columns: the first one writes it)
+        if (blockIdx.y == 0) ((R *)cy.lp_out)[p] = lp;
+#pragma unroll
+        for (int c = 0; c < TB; ++c)
+            if (j0 + c < a.T) ((R *)cy.base_out)[(size_t)(j0 + c) * a.npx + p] = b[c];
+    }
 
     // ---- wave sums, workgroup sums, one integer atomic per column and polarity.  64 lanes of 32-bit counts sum to up to 38 bits:
     // the 16-bit halves are summed apart (each sum stays below 2^22) and put together in 64 bits.
@@ -212,22 +251,27 @@ __global__ __launch_bounds__(BLOCK) void k_sweep(SweepArgs a)
     }
 }
 
-typedef void (*SweepKernel)(SweepArgs);
+typedef void (*SweepKernel)(SweepArgs, SweepCarry);
 
-template <typename R, bool SCALAR> SweepKernel pick_tb(int tb)
+template <typename R, bool SCALAR, bool CARRY> SweepKernel pick_tb(int tb)
 {
     switch (tb) {
-    case 4: return k_sweep<R, 4, SCALAR>;
-    case 8: return k_sweep<R, 8, SCALAR>;
-    case 16: return k_sweep<R, 16, SCALAR>;
+    case 4: return k_sweep<R, 4, SCALAR, CARRY>;
+    case 8: return k_sweep<R, 8, SCALAR, CARRY>;
+    case 16: return k_sweep<R, 16, SCALAR, CARRY>;
     default: return nullptr;
     }
 }
 
-SweepKernel pick_kernel(bool f64, bool scalar, int tb)
+template <bool CARRY> SweepKernel pick_carry(bool f64, bool scalar, int tb)
 {
-    if (f64) return scalar ? pick_tb<double, true>(tb) : pick_tb<double, false>(tb);
-    return scalar ? pick_tb<float, true>(tb) : pick_tb<float, false>(tb);
+    if (f64) return scalar ? pick_tb<double, true, CARRY>(tb) : pick_tb<double, false, CARRY>(tb);
+    return scalar ? pick_tb<float, true, CARRY>(tb) : pick_tb<float, false, CARRY>(tb);
+}
+
+SweepKernel pick_kernel(bool f64, bool scalar, int tb, bool carry = false)
+{
+    return carry ? pick_carry<true>(f64, scalar, tb) : pick_carry<false>(f64, scalar, tb);
 }
 
 constexpr int SWEEP_TB_DEFAULT = 8; // columns per thread where the caller names none (profiles/r14_threshold_sweep.txt)
@@ -243,17 +287,17 @@ struct SweepScratch {
 std::mutex g_mu;
 SweepScratch g_scratch[64];
 
-} // namespace
-
-extern "C" {
-
-int v2e_thres_sweep(const void *frames, int frame_dtype, int F, int H, int W, const double *t_frames, const v2e_sweep_params *p,
-                    const double *pos, const double *neg, int T, const int roi[4], uint64_t *counts_dev, int32_t *rule_on_dev,
-                    void *stream)
+// Both entry points.  cy == nullptr: the whole clip (CARRY = false; counts and flags start from zero); otherwise the chunk whose first frame
+// is the clip's frame cy->frame0 (CARRY = true; counts are added to, flags OR-ed into).  t_previous: the emulator's t_previous when
+// it is given frames[0] -- 0 for the clip's first two frames (the first frame does not advance it, emulator.py:717).
+int sweep_enqueue(const void *frames, int frame_dtype, int F, int H, int W, const double *t_frames, const SweepCarry *cy, double t_previous,
+                  const v2e_sweep_params *p, const double *pos, const double *neg, int T, const int roi[4], uint64_t *counts_dev,
+                  int32_t *rule_on_dev, void *stream)
 {
+    const bool first = !cy || cy->frame0 == 0u; // frames[0] is the clip's first frame
     V2E_REQUIRE(frames && t_frames && p && pos && neg && roi && counts_dev && rule_on_dev, "null argument");
     V2E_REQUIRE(frame_dtype == V2E_DT_U8, "the sweep reads uint8 frames only");
-    V2E_REQUIRE(F >= 2, "a sweep needs at least two frames (the first one initialises the state)");
+    V2E_REQUIRE(F >= (cy ? 1 : 2), cy ? "a chunk needs at least one frame" : "a sweep needs at least two frames (the first one initialises the state)");
     V2E_REQUIRE(T >= 1, "no thresholds");
     V2E_REQUIRE(H > 0 && W > 0 && (long long)H * W <= 0x7FFFFF00ll, "bad sensor size");
     V2E_REQUIRE(roi[0] >= 0 && roi[0] <= roi[1] && roi[1] < W && roi[2] >= 0 && roi[2] <= roi[3] && roi[3] < H,
@@ -266,23 +310,30 @@ int v2e_thres_sweep(const void *frames, int frame_dtype, int F, int H, int W, co
                 "bad model parameters");
     const int tb = p->cols_per_thread ? p->cols_per_thread : SWEEP_TB_DEFAULT;
     const bool f64 = p->cutoff_hz > 0, scalar = !(p->sigma_thres > 0);
-    const SweepKernel kern = pick_kernel(f64, scalar, tb);
+    const SweepKernel kern = pick_kernel(f64, scalar, tb, cy != nullptr);
     V2E_REQUIRE(kern, "cols_per_thread must be 0 (default), 4, 8 or 16");
     V2E_REQUIRE((T + tb - 1) / tb <= 65535, "too many thresholds");
+    if (cy) {
+        V2E_REQUIRE(cy->lp_out && cy->base_out && (first || (cy->lp_in && cy->base_in)), "null state plane");
+        V2E_REQUIRE(cy->lp_out != cy->lp_in && cy->base_out != cy->base_in, "the state is written to other planes than it is read from");
+        V2E_REQUIRE((unsigned long long)cy->frame0 + (unsigned long long)F <= 0x7FFFFFFFull, "frame index out of range");
+    }
     // a fresh emulator's frames: the first one at t[0] >= 0 = t_previous, which it does not advance (emulator.py:717); every
     // later one strictly after the one before
     V2E_REQUIRE(std::isfinite(t_frames[0]) && t_frames[0] >= 0, "the first frame time must be finite and not negative");
+    V2E_REQUIRE(first ? t_previous == 0.0 : (std::isfinite(t_previous) && t_previous >= 0), "bad t_previous");
     std::vector<unsigned char> host(sizeof(SweepFrame) * (size_t)F + 2 * sizeof(double) * (size_t)T);
     SweepFrame *tab = (SweepFrame *)host.data();
     double *thr = (double *)(host.data() + sizeof(SweepFrame) * (size_t)F);
-    double t_prev = 0.0;
+    double t_prev = t_previous;
     for (int f = 0; f < F; ++f) {
-        V2E_REQUIRE(std::isfinite(t_frames[f]) && (f == 0 || (t_frames[f] > t_prev && t_frames[f] > t_frames[f - 1])), "frame times must increase");
+        V2E_REQUIRE(std::isfinite(t_frames[f]) && ((first && f == 0) || t_frames[f] > t_prev) && (f == 0 || t_frames[f] > t_frames[f - 1]),
+                    "frame times must increase");
         const FrameCtl c = make_ctl(t_prev, t_frames[f], p->cutoff_hz, 0.0, p->refractory_period_s);
         tab[f].dt_over_tau = c.dt_over_tau;
         tab[f].dtime_f = (float)(c.t_frame - c.t_prev);
         tab[f].refr_on_n = c.refr_on_n;
-        if (f > 0) t_prev = t_frames[f];
+        if (!(first && f == 0)) t_prev = t_frames[f];
     }
     for (int j = 0; j < T; ++j) { thr[j] = pos[j]; thr[T + j] = neg[j]; }
 
@@ -304,8 +355,10 @@ int v2e_thres_sweep(const void *frames, int frame_dtype, int F, int H, int W, co
     sc.last = s; sc.used = true;
     // (pageable source: the copy has left `host` when the call returns)
     V2E_HIP(hipMemcpyAsync(sc.dev, host.data(), host.size(), hipMemcpyHostToDevice, s));
-    V2E_HIP(hipMemsetAsync(counts_dev, 0, sizeof(uint64_t) * 2 * (size_t)T, s));
-    V2E_HIP(hipMemsetAsync(rule_on_dev, 0, sizeof(int32_t) * (size_t)T, s));
+    if (!cy) {
+        V2E_HIP(hipMemsetAsync(counts_dev, 0, sizeof(uint64_t) * 2 * (size_t)T, s));
+        V2E_HIP(hipMemsetAsync(rule_on_dev, 0, sizeof(int32_t) * (size_t)T, s));
+    }
 
     SweepArgs a;
     memset(&a, 0, sizeof(a));
@@ -321,15 +374,15 @@ int v2e_thres_sweep(const void *frames, int frame_dtype, int F, int H, int W, co
     a.seed = p->seed;
     a.counts = (unsigned long long *)counts_dev; a.rule_on = (int *)rule_on_dev;
     const dim3 grid((unsigned)v2e_cdiv(a.npx, BLOCK), (unsigned)((T + tb - 1) / tb));
-    kern<<<grid, BLOCK, 0, s>>>(a);
+    kern<<<grid, BLOCK, 0, s>>>(a, cy ? *cy : SweepCarry());
     V2E_HIP(hipGetLastError());
     return 0;
 }
 
-int v2e_thres_sweep_info(int f64_state, int scalar_thres, int cols_per_thread, int *cols_out, int *vgprs, int *workgroups_per_cu)
+int sweep_info(bool carry, int f64_state, int scalar_thres, int cols_per_thread, int *cols_out, int *vgprs, int *workgroups_per_cu)
 {
     const int tb = cols_per_thread ? cols_per_thread : SWEEP_TB_DEFAULT;
-    const SweepKernel kern = pick_kernel(f64_state != 0, scalar_thres != 0, tb);
+    const SweepKernel kern = pick_kernel(f64_state != 0, scalar_thres != 0, tb, carry);
     V2E_REQUIRE(kern, "cols_per_thread must be 0 (default), 4, 8 or 16");
     if (cols_out) *cols_out = tb;
     if (vgprs) {
@@ -339,6 +392,39 @@ int v2e_thres_sweep_info(int f64_state, int scalar_thres, int cols_per_thread, i
     }
     if (workgroups_per_cu) V2E_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(workgroups_per_cu, (const void *)kern, BLOCK, 0));
     return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int v2e_thres_sweep(const void *frames, int frame_dtype, int F, int H, int W, const double *t_frames, const v2e_sweep_params *p,
+                    const double *pos, const double *neg, int T, const int roi[4], uint64_t *counts_dev, int32_t *rule_on_dev,
+                    void *stream)
+{
+    return sweep_enqueue(frames, frame_dtype, F, H, W, t_frames, nullptr, 0.0, p, pos, neg, T, roi, counts_dev, rule_on_dev, stream);
+}
+
+int v2e_thres_sweep_chunk(const void *frames, int frame_dtype, int F, int H, int W, const double *t_frames, int64_t frame0,
+                          double t_previous, const v2e_sweep_params *p, const double *pos, const double *neg, int T, const int roi[4],
+                          const void *lp_in, const void *base_in, void *lp_out, void *base_out, uint64_t *counts_dev,
+                          int32_t *rule_on_dev, void *stream)
+{
+    V2E_REQUIRE(frame0 >= 0 && frame0 <= 0x7FFFFFFFll, "frame0 out of range");
+    SweepCarry cy;
+    cy.frame0 = (uint32_t)frame0;
+    cy.lp_in = lp_in; cy.base_in = base_in; cy.lp_out = lp_out; cy.base_out = base_out;
+    return sweep_enqueue(frames, frame_dtype, F, H, W, t_frames, &cy, t_previous, p, pos, neg, T, roi, counts_dev, rule_on_dev, stream);
+}
+
+int v2e_thres_sweep_info(int f64_state, int scalar_thres, int cols_per_thread, int *cols_out, int *vgprs, int *workgroups_per_cu)
+{
+    return sweep_info(false, f64_state, scalar_thres, cols_per_thread, cols_out, vgprs, workgroups_per_cu);
+}
+
+int v2e_thres_sweep_chunk_info(int f64_state, int scalar_thres, int cols_per_thread, int *cols_out, int *vgprs, int *workgroups_per_cu)
+{
+    return sweep_info(true, f64_state, scalar_thres, cols_per_thread, cols_out, vgprs, workgroups_per_cu);
 }
 
 } // extern "C"

@@ -300,7 +300,7 @@ class VideoToEvents:
         return self._streams[name]
 
     def run_stream(self, frames_u8, src_frame_interval_s, chunk_pairs=None, on_events=None, return_device=False, cap=None,
-                   renderer=None, on_dvs_frames=None, dvs_u8=False):
+                   renderer=None, on_dvs_frames=None, dvs_u8=False, on_frames=None):
         """The clip through the whole pipeline in chunks of `chunk_pairs` source pairs on one GPU, with device memory bounded by the
         chunk, not the clip; returns (events, counts_per_interpolated_frame, n_interpolated_frames) as `run` does, with the same
         events, counts, frame order, frame times, event files and (auto_upsample) `upsampling_factors`, `interpTimes` and
@@ -325,6 +325,12 @@ class VideoToEvents:
         stream is ordered before the buffer is reused).  Without on_events the rows are gathered (device rows copied out of the
         emulator's buffers) and returned as `run` returns them.
 
+        on_frames(frames, times, frame0): called once per chunk, in frame order, on the caller's stream (which has been ordered
+        behind the chunk's SloMo stage) before the chunk's emulator run is enqueued, with the very uint8 tensor [F,H,W] the emulator
+        is about to read, the F frame times and the index of the chunk's first interpolated frame -- ThresholdSweep.add_run takes
+        it as it is.  The tensor is valid for the duration of the callback only: work the callback enqueues on the current stream
+        reads it before its memory is reused, anything else has to copy it.  Without on_frames nothing changes.
+
         renderer: a v2e_amd.EventRenderer -- every chunk's DVS frames (EventRenderer.render_run with the chunk's first frame
         index, so the packets are the clip's, whatever the chunking) are rendered behind that chunk's result() on a stream of
         their own, which the emulator's runs do not wait for until they reuse the chunk's row buffer; the leftover events are
@@ -338,4 +344,4 @@ class VideoToEvents:
         sample index runs on over the chunk boundaries; `emu.cleanup()` writes the file): every chunk is then a probed run, on the
         per-frame kernels and not pipelined (EventEmulator.generate_events_batch_async)."""
         return StreamRun(self, frames_u8, src_frame_interval_s, chunk_pairs, on_events, return_device, cap, renderer, on_dvs_frames,
-                         dvs_u8).run()
+                         dvs_u8, on_frames).run()

@@ -54,13 +54,13 @@ class StreamRun:
     the at most two emulator runs in flight as (handle, the chunk's frames, index of its first frame)."""
 
     def __init__(self, pipe, frames_u8, src_frame_interval_s, chunk_pairs, on_events, return_device, cap, renderer, on_dvs_frames,
-                 dvs_u8):
+                 dvs_u8, on_frames=None):
         """Checks the clip and the chunking, then readies the streams, the host frame feed and -- where it is known before the
         first chunk -- the time scale, and resets the pipeline's per-clip results."""
         N, self.H, self.W = stream_source_shape(frames_u8)
         chunks = self.chunks = stream_chunks(N - 1, pipe.batch_size, chunk_pairs)
         self.pipe, self.frames, self.N, self.dt = pipe, frames_u8, N, float(src_frame_interval_s)
-        self.on_events, self.return_device, self.cap = on_events, return_device, cap
+        self.on_events, self.return_device, self.cap, self.on_frames = on_events, return_device, cap, on_frames
         self.renderer, self.on_dvs_frames, self.dvs_u8 = renderer, on_dvs_frames, dvs_u8
         self.runs, self.rows, self.counts, self.factors, self.dvs = [], [], [], [], []
         self.run_cap = self.nfr = 0
@@ -137,6 +137,12 @@ class StreamRun:
             #                   first frame is the initial state) and a set sized for that would be regrown by the third run
             self.run_cap = max(self.run_cap, default_event_capacity(int(up.shape[0]), self.H, self.W))
         self.main.wait_event(ready)
+        if self.on_frames is not None:
+            # The chunk's frames before its run is enqueued: what the callback enqueues on the caller's stream reads them ahead of
+            # the run's chain.  `up` belongs to the side stream's allocator and must not return to it before that work has read
+            # it; it is kept with the run's entry until collect() has the run's result, and the host has then waited for rows
+            # that the chain wrote behind the callback's work on the same stream.
+            self.on_frames(up, times, self.nfr)
         # (pipelined runs overlap run after run on streams of the emulator's, which it assigns by a probe on its first such
         #  run; a clip of one chunk has nothing to overlap and runs as run()'s does, plain launches on the caller's stream)
         pend = pipe.emu.generate_events_batch_async(up, times, return_device=True, use_graph=0,

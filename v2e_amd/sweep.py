@@ -19,8 +19,22 @@ it were off and flags the columns in which it would have switched on, and those 
 (`SweepResult.rule_on` says which).  The sums over pixels are 64-bit; the one limit is a single pixel's own ON (or OFF) total of
 a column over the whole clip, which the kernel keeps in 32 bits: beyond 2^32 - 1 events of one polarity on one pixel it wraps.
 
+A clip of any length goes through chunk by chunk: `add_run(frames, t, frame0)` sweeps the clip's next frames and `result()` returns
+the counts of all frames so far, the same integers `run` gives for them as one clip however the clip is cut.  The kernel
+(v2e_thres_sweep_chunk) carries lp_log_frame and every column's base_log_frame from call to call in two sets of device planes that
+alternate as its input and output -- it never writes what it reads -- adds to the counts and ORs into the flags, and keys Philox by
+the clip's frame index.  With refractory_period_s == 0 no flag can rise and add_run never waits for the device.  Otherwise it reads
+the T flags back after each call.  While the rule has never been on in a column, timestamp_mem is neither read nor written
+(sweep.hip), so when a column's flag first rises in a chunk its state at the START of that chunk is still exact, and still there.
+That column leaves the kernel: what the kernel added to it in this chunk is dropped, and from the chunk's first frame on it is
+computed by the emulator itself, primed with the carried lp and base planes, an untouched timestamp_mem, the column's thresholds,
+frame_counter = frame0 and the previous frame's time as t_previous, for the rest of the clip (`SweepResult.rule_on_from`).  One
+emulator is shared by all such columns, their own state planes copied in and out around each block of frames
+(`_advance_columns`).  `reset()` readies the instance for the next clip.  VideoToEvents.run_stream and SyntheticToEvents.run hand
+each chunk's frames to `add_run` through their `on_frames` hook.
+
 Out of scope: shot noise (it resets base_log_frame per column and adds rows), hdr, float frames, photoreceptor_noise, SCIDVS,
-CSDVS, tape mode, a clip streamed across several `run` calls, per-frame or per-pixel count maps, reading recordings.
+CSDVS, tape mode, per-frame or per-pixel count maps, reading recordings, multi-rank runs.
 """
 import ctypes as C
 import math
@@ -35,14 +49,47 @@ RECOMPUTE_BLOCK_FRAMES = 32  # frames per emulator run when a rule-on column is 
 
 
 class SweepResult(object):
-    """on, off: numpy int64 [T]; rule_on: numpy bool [T], True where the column was recomputed by the emulator because the
-    refractory rule switched on."""
+    """on, off: numpy int64 [T]; rule_on: numpy bool [T], True where the column was computed by the emulator because the
+    refractory rule switched on; rule_on_from: numpy int64 [T], the clip's index of the first frame the emulator computed in that
+    column -- the `frame0` of the chunk in which it left the kernel (0 from `run`) -- and -1 where rule_on is False."""
 
-    def __init__(self, on, off, rule_on):
+    def __init__(self, on, off, rule_on, rule_on_from=None):
         self.on, self.off, self.rule_on = on, off, rule_on
+        self.rule_on_from = np.where(rule_on, 0, -1).astype(np.int64) if rule_on_from is None else rule_on_from
 
     def __repr__(self):
-        return "SweepResult(on=%r, off=%r, rule_on=%r)" % (self.on, self.off, self.rule_on)
+        return "SweepResult(on=%r, off=%r, rule_on=%r, rule_on_from=%r)" % (self.on, self.off, self.rule_on, self.rule_on_from)
+
+
+def check_continuation(frames_seen, t_last, t_frames, frame0=None):
+    """The chunk with frame times t_frames continues a clip of which frames_seen frames have been swept, the last one at time
+    t_last (ignored while frames_seen is 0): returns the clip's index of the chunk's first frame, which is frames_seen.  ValueError
+    for an empty chunk, a frame0 that is given and is not frames_seen (a gap or an overlap), times that are not finite or do not
+    increase inside the chunk, a first time that is negative, or one that is not after t_last."""
+    t = np.asarray(t_frames, dtype=np.float64).reshape(-1)
+    frames_seen = int(frames_seen)
+    if len(t) < 1:
+        raise ValueError("ThresholdSweep.add_run: a chunk has at least one frame")
+    if frame0 is not None and int(frame0) != frames_seen:
+        raise ValueError("ThresholdSweep.add_run: the chunk begins at frame %d of the clip but %d frames have been swept (%s)"
+                         % (int(frame0), frames_seen, "a gap" if int(frame0) > frames_seen else "an overlap"))
+    if not (np.all(np.isfinite(t)) and t[0] >= 0 and np.all(np.diff(t) > 0)):
+        raise ValueError("ThresholdSweep.add_run: frame times must be finite, not negative and increasing")
+    if frames_seen > 0 and not t[0] > float(t_last):
+        raise ValueError("ThresholdSweep.add_run: the chunk's first frame time %r is not after the last frame swept, %r"
+                         % (float(t[0]), float(t_last)))
+    return frames_seen
+
+
+class _EmuColumn(object):
+    """A column of a streamed sweep that the emulator computes (the refractory rule switched on in it).  acc: device int64 [2], its
+    ON / OFF counts so far; base0: its base_log_frame [H*W] at the start of the chunk in which it left the kernel (None: it left
+    in the clip's first chunk and starts as a fresh emulator); planes: what the shared emulator's state planes held after this
+    column's last block -- base_log_frame, timestamp_mem and the two threshold planes, padded as the engine holds them (None before
+    its first block)."""
+
+    def __init__(self, acc, base0):
+        self.acc, self.base0, self.planes = acc, base0, None
 
 
 def _thresholds(values, what):
@@ -98,6 +145,10 @@ class ThresholdSweep(object):
         self.max_iters = int(max_iters)
         self.device = torch.device(device)
         self.recomputed_columns = 0  # columns of the last run that took the emulator path
+        # the streamed sweep (add_run / result / reset): two sets of state planes (lp [npx], base [T][npx]) that alternate as the
+        # kernel's input and output, the counts and flags it adds to, the emulator shared by the rule-on columns
+        self._planes = self._counts = self._rule = self._emu = None
+        self.reset()
 
     @classmethod
     def from_emulator(cls, emu, thresholds, neg_thresholds=None, *, roi=None, height=None, width=None, device=None, **kw):
@@ -121,23 +172,24 @@ class ThresholdSweep(object):
                    seed=emu.seed, device=emu.device if device is None else device, **kw)
 
     # ------------------------------------------------------------------------------------------------------------ run
-    def _check_frames(self, frames, t_frames):
+    def _check_frames(self, frames, t_frames, what="run", min_frames=2):
         if not torch.is_tensor(frames):
-            raise ValueError("ThresholdSweep.run: frames must be a device tensor [F,H,W] of uint8 (host arrays are not swept: "
-                             "upload them once)")
+            raise ValueError("ThresholdSweep.%s: frames must be a device tensor [F,H,W] of uint8 (host arrays are not swept: "
+                             "upload them once)" % what)
         if not frames.is_cuda:
-            raise ValueError("ThresholdSweep.run: frames are on the host; the sweep reads them from device memory")
+            raise ValueError("ThresholdSweep.%s: frames are on the host; the sweep reads them from device memory" % what)
         if frames.dtype != torch.uint8:
-            raise ValueError("ThresholdSweep.run: frames must be uint8, got %s" % (frames.dtype,))
+            raise ValueError("ThresholdSweep.%s: frames must be uint8, got %s" % (what, frames.dtype))
         if frames.dim() != 3 or tuple(frames.shape[1:]) != (self.height, self.width):
-            raise ValueError("ThresholdSweep.run: frames must be [F,%d,%d], got %r" % (self.height, self.width, tuple(frames.shape)))
+            raise ValueError("ThresholdSweep.%s: frames must be [F,%d,%d], got %r" % (what, self.height, self.width, tuple(frames.shape)))
         t = np.array([float(v) for v in t_frames], dtype=np.float64)
         if len(t) != frames.shape[0]:
-            raise ValueError("ThresholdSweep.run: need one timestamp per frame")
-        if len(t) < 2:
-            raise ValueError("ThresholdSweep.run: at least two frames (the first one initialises the emulator)")
+            raise ValueError("ThresholdSweep.%s: need one timestamp per frame" % what)
+        if len(t) < min_frames:
+            raise ValueError("ThresholdSweep.run: at least two frames (the first one initialises the emulator)" if min_frames == 2 else
+                             "ThresholdSweep.add_run: a chunk has at least one frame")
         if not (np.all(np.isfinite(t)) and t[0] >= 0 and np.all(np.diff(t) > 0)):
-            raise ValueError("ThresholdSweep.run: frame times must be finite, not negative and increasing")
+            raise ValueError("ThresholdSweep.%s: frame times must be finite, not negative and increasing" % what)
         return t
 
     def run(self, frames, t_frames):
@@ -150,12 +202,7 @@ class ThresholdSweep(object):
         dev = frames.device
         frames = frames.contiguous()
         F, T = int(frames.shape[0]), len(self.thresholds)
-        P = _capi.SweepParams()
-        P.sigma_thres, P.cutoff_hz, P.leak_rate_hz = self.sigma_thres, self.cutoff_hz, self.leak_rate_hz
-        P.leak_jitter_fraction, P.noise_rate_cov_decades = self.leak_jitter_fraction, self.noise_rate_cov_decades
-        P.refractory_period_s = self.refractory_period_s
-        P.seed = self.seed & 0xFFFFFFFFFFFFFFFF
-        P.cols_per_thread = self.cols_per_thread
+        P = self._sweep_params()
         (x0, x1), (y0, y1) = self.roi
         with torch.cuda.device(dev):
             counts = torch.empty((T, 2), dtype=torch.int64, device=dev)
@@ -174,15 +221,28 @@ class ThresholdSweep(object):
         self.recomputed_columns = int(rule_on.sum())
         return SweepResult(on, off, rule_on)
 
+    def _sweep_params(self):
+        P = _capi.SweepParams()
+        P.sigma_thres, P.cutoff_hz, P.leak_rate_hz = self.sigma_thres, self.cutoff_hz, self.leak_rate_hz
+        P.leak_jitter_fraction, P.noise_rate_cov_decades = self.leak_jitter_fraction, self.noise_rate_cov_decades
+        P.refractory_period_s = self.refractory_period_s
+        P.seed = self.seed & 0xFFFFFFFFFFFFFFFF
+        P.cols_per_thread = self.cols_per_thread
+        return P
+
+    def _new_emulator(self, j, device):
+        """The emulator column j is: Philox mode, the sweep's model parameters, no shot noise."""
+        from .emulator import EventEmulator
+        return EventEmulator(pos_thres=float(self.thresholds[j]), neg_thres=float(self.neg_thresholds[j]), sigma_thres=self.sigma_thres,
+                             cutoff_hz=self.cutoff_hz, leak_rate_hz=self.leak_rate_hz, refractory_period_s=self.refractory_period_s,
+                             shot_noise_rate_hz=0.0, leak_jitter_fraction=self.leak_jitter_fraction,
+                             noise_rate_cov_decades=self.noise_rate_cov_decades, seed=self.seed, device=str(device),
+                             rng_mode="philox", max_iters=self.max_iters)
+
     def _recompute_column(self, j, frames, t):
         """The exact path of a column in which the refractory rule switched on: a fresh Philox-mode emulator over the same frames, in
         blocks (it carries its state from run to run), its rows counted in the ROI on the device."""
-        from .emulator import EventEmulator
-        emu = EventEmulator(pos_thres=float(self.thresholds[j]), neg_thres=float(self.neg_thresholds[j]), sigma_thres=self.sigma_thres,
-                            cutoff_hz=self.cutoff_hz, leak_rate_hz=self.leak_rate_hz, refractory_period_s=self.refractory_period_s,
-                            shot_noise_rate_hz=0.0, leak_jitter_fraction=self.leak_jitter_fraction,
-                            noise_rate_cov_decades=self.noise_rate_cov_decades, seed=self.seed, device=str(frames.device),
-                            rng_mode="philox", max_iters=self.max_iters)
+        emu = self._new_emulator(j, frames.device)
         try:
             acc = torch.zeros((2,), dtype=torch.int64, device=frames.device)
             for a in range(0, len(t), RECOMPUTE_BLOCK_FRAMES):
@@ -193,6 +253,155 @@ class ThresholdSweep(object):
         finally:
             emu.cleanup()
         return on, off
+
+    # ------------------------------------------------------------------------------------------------------- streamed
+    def reset(self):
+        """Ready for the next clip: the carried state, the counts and the flags start over, and the emulator of the rule-on columns
+        is released with the planes kept for them."""
+        self.frames_seen = 0  # frames of the clip swept so far
+        self.host_syncs = 0   # read-backs add_run and result have waited for (the runs of a rule-on column's emulator wait besides)
+        self._t_last = None   # the time of the last frame swept
+        self._cur = 0         # which set of state planes holds the state behind the last frame swept
+        self._cols = {}       # column -> _EmuColumn, in the order the columns left the kernel
+        self._rule_on_from = np.full(len(self.thresholds), -1, dtype=np.int64)
+        if self._counts is not None:
+            self._counts.zero_()
+            self._rule.zero_()
+        if self._emu is not None:
+            self._emu.cleanup()
+            self._emu = None
+
+    def add_run(self, frames, t_frames, frame0=None):
+        """The clip's next chunk: frames uint8 [F,H,W] on the device, F >= 1, with their F times.  The first call after
+        construction or reset() brings the clip's first frames; every later one continues where the one before ended (frame0, when
+        given, is the number of frames swept so far, and the times go on increasing: `check_continuation`).  The signature is that
+        of the `on_frames` hook of VideoToEvents.run_stream and SyntheticToEvents.run.
+
+        Enqueued on the current stream behind whatever produced the frames; every call of a clip is to be made on the same stream
+        (or ordered behind the one before by the caller).  The frames have been read when the work enqueued here has run, so a
+        producer that reuses their buffer orders that behind the current stream.  With refractory_period_s == 0 no flag can rise
+        and the call does not wait for the device.  Otherwise it reads the T flags back (one small read-back, counted in
+        host_syncs), and a column whose flag has risen is computed by the emulator from the start of this chunk on, for the rest
+        of the clip (module docstring); those runs wait for their events."""
+        t = self._check_frames(frames, t_frames, "add_run", 1)
+        frame0 = check_continuation(self.frames_seen, self._t_last, t, frame0)
+        if not torch.cuda.is_available():
+            raise _capi.V2EAmdError("v2e_amd.ThresholdSweep needs a ROCm GPU; there is no CPU fallback")
+        lib = _capi.lib()
+        dev = frames.device
+        frames = frames.contiguous()
+        F, T, npx = int(frames.shape[0]), len(self.thresholds), self.height * self.width
+        P = self._sweep_params()
+        (x0, x1), (y0, y1) = self.roi
+        refr = self.refractory_period_s > 0
+        # the emulator's t_previous when it is given the chunk's first frame: the clip's first frame does not advance it
+        t_prev = float(self._t_last) if frame0 > 1 else 0.0
+        with torch.cuda.device(dev):
+            if self._planes is not None and self._counts.device != dev:
+                if self.frames_seen:
+                    raise ValueError("ThresholdSweep.add_run: the clip's state is on %s, this chunk on %s" % (self._counts.device, dev))
+                self._planes = None
+            if self._planes is None:
+                R = torch.float64 if self.cutoff_hz > 0 else torch.float32
+                self._planes = [(torch.empty((npx,), dtype=R, device=dev), torch.empty((T, npx), dtype=R, device=dev)) for _ in range(2)]
+                self._counts = torch.zeros((T, 2), dtype=torch.int64, device=dev)
+                self._rule = torch.zeros((T,), dtype=torch.int32, device=dev)
+            (lp_in, base_in), (lp_out, base_out) = self._planes[self._cur], self._planes[1 - self._cur]
+            before = self._counts.clone() if refr else None  # what a column that leaves the kernel in this chunk keeps
+            check(lib.v2e_thres_sweep_chunk(C.c_void_p(frames.data_ptr()), _capi.DT_U8, F, self.height, self.width,
+                                            t.ctypes.data_as(C.POINTER(C.c_double)), frame0, t_prev, C.byref(P),
+                                            self.thresholds.ctypes.data_as(C.POINTER(C.c_double)),
+                                            self.neg_thresholds.ctypes.data_as(C.POINTER(C.c_double)), T,
+                                            (C.c_int * 4)(x0, x1, y0, y1), C.c_void_p(lp_in.data_ptr()), C.c_void_p(base_in.data_ptr()),
+                                            C.c_void_p(lp_out.data_ptr()), C.c_void_p(base_out.data_ptr()),
+                                            C.c_void_p(self._counts.data_ptr()), C.c_void_p(self._rule.data_ptr()),
+                                            _capi.stream_ptr(dev)), "v2e_thres_sweep_chunk")
+            if refr:
+                rule_on = self._rule.cpu().numpy() != 0
+                self.host_syncs += 1
+                for j in (int(j) for j in np.nonzero(rule_on)[0] if int(j) not in self._cols):
+                    # the state the kernel read is still there (it writes the other set): exact, the rule never having been on
+                    self._cols[j] = _EmuColumn(before[j].clone(), None if frame0 == 0 else base_in[j].clone())
+                    self._rule_on_from[j] = frame0
+                if self._cols:
+                    self._advance_columns(frames, t, frame0, t_prev, None if frame0 == 0 else lp_in)
+        self._cur ^= 1
+        self.frames_seen += F
+        self._t_last = float(t[-1])
+
+    def result(self):
+        """A SweepResult of all frames swept so far: what `run` returns for them as one clip.  The one read-back of the counts
+        (counted in host_syncs); the sweep goes on with the next add_run."""
+        T = len(self.thresholds)
+        rule_on = np.zeros(T, dtype=bool)
+        rule_on[list(self._cols)] = True
+        if self._counts is None:
+            return SweepResult(np.zeros(T, np.int64), np.zeros(T, np.int64), rule_on, self._rule_on_from.copy())
+        with torch.cuda.device(self._counts.device):
+            host = torch.cat([self._counts.reshape(-1)] + [col.acc for col in self._cols.values()]).cpu().numpy()
+        self.host_syncs += 1
+        on, off = host[0:2 * T:2].copy(), host[1:2 * T:2].copy()
+        for k, j in enumerate(self._cols):  # the kernel's additions since the column left it are not the column's
+            on[j], off[j] = host[2 * T + 2 * k], host[2 * T + 2 * k + 1]
+        return SweepResult(on, off, rule_on, self._rule_on_from.copy())
+
+    def _advance_columns(self, frames, t, frame0, t_prev, lp):
+        """The rule-on columns through the chunk, by the emulator itself (Philox mode) in blocks of RECOMPUTE_BLOCK_FRAMES frames,
+        their rows counted in the ROI.  One emulator serves them all: between two runs its handle keeps nothing of a column but
+        the six state planes it was bound (v2e_emu_bind_state; the second set of planes a refractory chain alternates with is
+        copied back before a run ends) -- of which lp_log_frame and the noise rate are the same in every column -- and the host
+        object keeps the thresholds, the frame counter and t_previous.  So per block every column's four own planes are copied in
+        and out around its run, and device memory grows by those planes per column, not by an emulator with its event buffers.
+        lp: lp_log_frame [H*W] at the start of the chunk (the kernel's carried plane; None: the chunk begins the clip)."""
+        if self._emu is None:
+            self._emu = self._new_emulator(next(iter(self._cols)), frames.device)
+        emu, npx = self._emu, self.height * self.width
+        for a in range(0, len(t), RECOMPUTE_BLOCK_FRAMES):
+            b = min(a + RECOMPUTE_BLOCK_FRAMES, len(t))
+            lp_next = None
+            for j, col in self._cols.items():
+                self._load_column(emu, j, col, frame0 + a, t_prev, lp, frames[a])
+                ev, _ = emu.generate_events_batch(frames[a:b], t[a:b], return_device=True)
+                if ev is not None and ev.shape[0]:
+                    col.acc += count_rows_in_roi(ev, self.roi)  # (before the next run reuses the event buffer)
+                eng = emu._engine
+                own = (eng.base, eng.ts_mem, eng.pos_thres, eng.neg_thres)
+                if col.planes is None:
+                    col.planes, col.base0 = [x.clone() for x in own], None
+                else:
+                    for dst, src in zip(col.planes, own):
+                        dst.copy_(src)
+                if lp_next is None:
+                    lp_next = eng.lp[0, :npx].clone()
+            lp = lp_next
+            t_prev = float(t[b - 1]) if frame0 + b > 1 else 0.0
+
+    def _load_column(self, emu, j, col, g0, t_prev, lp, frame):
+        """The shared emulator becomes column j about to be given the clip's frame g0."""
+        pj, nj = float(self.thresholds[j]), float(self.neg_thresholds[j])
+        npx = self.height * self.width
+        if col.planes is None:
+            # the column's first block: a fresh emulator -- which is all there is to it when the column left the kernel in the
+            # clip's first chunk.  Otherwise its first-frame step draws the column's threshold planes and the noise rate (k_init)
+            # and leaves timestamp_mem zero, untouched as the kernel's invariant has it; lp and base are then the carried ones
+            emu.reset()
+            emu.pos_thres = emu.pos_thres_nominal = pj
+            emu.neg_thres = emu.neg_thres_nominal = nj
+            emu.t_previous = 0
+            if g0 == 0:
+                return
+            emu._first_frame(frame, self.height, self.width, 0.0)
+            emu._engine.base[0, :npx].copy_(col.base0)
+        else:
+            eng = emu._engine
+            for dst, src in zip((eng.base, eng.ts_mem, eng.pos_thres, eng.neg_thres), col.planes):
+                dst.copy_(src)
+            emu.pos_thres_nominal, emu.neg_thres_nominal = pj, nj
+            emu._thres_scalar = (pj, nj)
+            if not self.sigma_thres > 0:
+                emu.pos_thres, emu.neg_thres = pj, nj
+        emu._engine.lp[0, :npx].copy_(lp)
+        emu.frame_counter, emu.t_previous = g0, t_prev
 
 
 def count_rows_in_roi(ev, roi):

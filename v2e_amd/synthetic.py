@@ -462,11 +462,15 @@ class SyntheticToEvents:
         self.source, self.emu, self.block_frames = source, emulator, int(block_frames)
         self._side = None  # run(): the stream the source renders on, created on first need
 
-    def run(self, on_events=None, return_device=False):
+    def run(self, on_events=None, return_device=False, on_frames=None):
         """Returns (events, counts per frame, n_frames).  on_events(events, counts, frame0) is called once per block in frame order
         (events None for a block without events on the host); nothing is accumulated then and events is None.  With
         return_device=True the rows are device tensors: inside on_events a view of one of the emulator's two alternating event
-        buffers, valid for the duration of the callback.
+        buffers, valid for the duration of the callback.  on_frames(frames, times, frame0) is called once per block in frame order,
+        on the caller's stream before the block's run is enqueued, with the very tensor [n,H,W] the emulator is about to read (one
+        of the two frame buffers), its frame times and the index of its first frame -- ThresholdSweep.add_run takes it as it is (a
+        uint8 source).  The tensor is valid for the duration of the callback only: work the callback enqueues on the current
+        stream reads it before the buffer is rendered into again, anything else has to copy it.  Without on_frames nothing changes.
 
         Two frame buffers alternate: block b + 1 is rendered on a stream of its own while the emulator runs block b.  The host waits
         for a block's render before it enqueues the block's run, so the run is enqueued with frames_resident=True (nothing on the
@@ -511,6 +515,10 @@ class SyntheticToEvents:
             for b in range(len(blocks)):
                 fr, t, ready = nxt
                 ready.synchronize()
+                if on_frames is not None:
+                    # (the buffer is rendered into again only behind read_done, which is recorded on the caller's stream below:
+                    #  behind the run's chain and so behind what the callback enqueued there, which must have read the frames)
+                    on_frames(fr, t, blocks[b][0])
                 pend = emu.generate_events_batch_async(fr, t, return_device=return_device, use_graph=0, cap=cap, frames_resident=True)
                 read_done[b & 1] = torch.cuda.Event()
                 read_done[b & 1].record(main)
