@@ -497,6 +497,63 @@ int64_t v2e_events_format_text_scratch_words(int64_t n);
 int v2e_events_format_text_host(const float *events, int64_t n, const v2e_frame_rec *recs, int nrec, int64_t n_signal,
                                 int labels, char *out, int64_t cap, int64_t *total);
 
+/* ----------------------------------------------------- event readers: the sinks inverted (v2e_amd/csrc/readers.hip) */
+
+/* items per workgroup of the readers' ordered compaction (records, and 16-byte pieces of text) */
+#define V2E_READER_BLOCK 1024
+/* counters of v2e_events_unpack_aedat2: device int64 [V2E_READER_COUNTERS], zeroed by the caller before a file's first call and
+ * accumulated over its calls; CALL_ROWS is set by each call to the rows it wrote, LAST_TS / HAVE_LAST carry the last kept time
+ * stamp to the next call so that a decreasing pair on a chunk boundary is counted. */
+#define V2E_READER_COUNTERS 8
+#define V2E_A2C_ROWS 0
+#define V2E_A2C_APS 1
+#define V2E_A2C_SPECIAL 2
+#define V2E_A2C_OUTSIDE 3
+#define V2E_A2C_NONMONOTONIC 4
+#define V2E_A2C_LAST_TS 5
+#define V2E_A2C_HAVE_LAST 6
+#define V2E_A2C_CALL_ROWS 7
+/* counters of v2e_events_parse_text (same rules): LINES every line seen; CALL_ROWS the rows this call wrote or -1 when the text
+ * has more lines than cap_rows (then CALL_LINES says how many and nothing else changed); CALL_FLAGGED the entries of `flagged`. */
+#define V2E_TXC_ROWS 0
+#define V2E_TXC_COMMENT 1
+#define V2E_TXC_BAD 2
+#define V2E_TXC_FLAGGED 3
+#define V2E_TXC_LINES 4
+#define V2E_TXC_CALL_ROWS 5
+#define V2E_TXC_CALL_LINES 6
+#define V2E_TXC_CALL_FLAGGED 7
+
+/* AEDAT-2.0 records back into rows, v2e_events_pack_aedat2 inverted: bytes holds n_records x 8 bytes (device, 8-byte aligned).
+ * A record with address bit 31 (APS / IMU) is dropped and counted (APS).  Address bit 10 (special event): special_mode 0 drops
+ * and counts it (SPECIAL: a jAER recording), 1 keeps it with labels[i] = 0 and 1 for every other row (a label_signal_noise file).
+ * Where bit 10 lies inside the x, y or p field (the 640x480 layout keeps x in bits 1 .. 10) it is data: no record is special,
+ * and special_mode 1 is refused.
+ * x = (addr >> xshift) & mask, mask the bits that hold 0 .. sizex - 1, un-flipped when flipx; y likewise; p = +1 with the
+ * polarity bit, else -1; t = (float)((double)ts * 1e-6); t_us[i] = ts (NULL: not wanted; labels likewise).  A row outside
+ * [0,sizex) x [0,sizey) is kept and counted (OUTSIDE); a kept record whose ts is below the kept one before it is counted
+ * (NONMONOTONIC).  Rows keep the records' order.  rows, labels, t_us: room for n_records rows (rows 16-byte aligned);
+ * scratch: device bytes [v2e_events_unpack_aedat2_scratch_bytes(n_records)], 16-byte aligned. */
+int v2e_events_unpack_aedat2(const void *bytes, int64_t n_records, int sizex, int sizey, int xshift, int yshift, int pshift,
+                             int flipx, int flipy, int special_mode, float *rows, uint8_t *labels, int64_t *t_us,
+                             int64_t *counters, void *scratch, void *stream);
+int64_t v2e_events_unpack_aedat2_scratch_bytes(int64_t n_records);
+
+/* Text lines back into rows, v2e_events_format_text inverted: bytes holds n_bytes of whole lines (device, 16-byte aligned); a
+ * line ends at '\n' (a '\r' before it is dropped), a last line without one counts.  Grammar and the exact decimal -> float32
+ * conversion of t (np.float32(float(s))): v2e_amd/csrc/text_parse.h.  Empty and '#' lines are counted (COMMENT), malformed
+ * ones too (BAD); want_labels != 0: a fifth field 0 / 1 is required and goes to labels.  A time stamp outside the domain the
+ * parser decides exactly (more than 19 significant digits, a decimal exponent outside +-62) still gives a row, with a best
+ * effort t, and an entry flagged[2 j] = the line's byte offset, flagged[2 j + 1] = its row index of this call (device int64
+ * [cap_flagged][2], in no particular order; CALL_FLAGGED may exceed cap_flagged, the entries beyond it are not written).
+ * rows / labels: room for cap_rows rows; scratch: device bytes [v2e_events_parse_text_scratch_bytes(n_bytes, cap_rows)]. */
+int v2e_events_parse_text(const char *bytes, int64_t n_bytes, int want_labels, float *rows, uint8_t *labels, int64_t cap_rows,
+                          int64_t *counters, int64_t *flagged, int64_t cap_flagged, void *scratch, void *stream);
+int64_t v2e_events_parse_text_scratch_bytes(int64_t n_bytes, int64_t cap_rows);
+/* The same on the host, from the same __host__ __device__ code: host bytes, rows, labels, counters and flagged, a plain loop. */
+int v2e_events_parse_text_host(const char *bytes, int64_t n_bytes, int want_labels, float *rows, uint8_t *labels,
+                               int64_t cap_rows, int64_t *counters, int64_t *flagged, int64_t cap_flagged);
+
 /* HDF5 "events" rows of emulator.py:955-965: uint32 [n][4] = (t*1e6 in float32, x, y, p with -1 -> 0) */
 int v2e_events_pack_h5(const float *events, uint32_t *out, int64_t n, void *stream);
 

@@ -159,6 +159,11 @@ SIGNATURES = {
     "v2e_events_format_text": (_i, [_vp, _i64, _vp, _i, _i64, _i, _vp, _i64, _vp, _vp]),
     "v2e_events_format_text_scratch_words": (_i64, [_i64]),
     "v2e_events_format_text_host": (_i, [_vp, _i64, _vp, _i, _i64, _i, _vp, _i64, C.POINTER(_i64)]),
+    "v2e_events_unpack_aedat2": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "v2e_events_unpack_aedat2_scratch_bytes": (_i64, [_i64]),
+    "v2e_events_parse_text": (_i, [_vp, _i64, _i, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "v2e_events_parse_text_scratch_bytes": (_i64, [_i64, _i64]),
+    "v2e_events_parse_text_host": (_i, [_vp, _i64, _i, _vp, _vp, _i64, _vp, _vp, _i64]),
     "v2e_events_pack_h5": (_i, [_vp, _vp, _i64, _vp]),
     "v2e_events_pack64": (_i, [_vp, _vp, _i64, _vp]),
     "v2e_events_unpack64": (_i, [_vp, _vp, _i64, _vp]),
