@@ -559,7 +559,10 @@ int v2e_events_pack_h5(const float *events, uint32_t *out, int64_t n, void *stre
 
 /* Lossless 8-byte wire format of an event row [t, x, y, p] (emulator.py:1024-1059 builds them as float32[4]):
  * bits 63..32 the float32 bits of t, 31..18 x, 17..4 y, bit 0 (p > 0); x, y < 16384.  Used by the multi-GPU
- * all-gather of the event streams (half the bytes over xGMI); unpack restores the float32 rows exactly. */
+ * all-gather of the event streams (half the bytes over xGMI); unpack restores the float32 rows exactly.
+ * Domain: x and y integer values in [0, 16384), p = +-1 (any p > 0 is restored as +1, any other as -1); t may be any float32,
+ * NaN payloads and -0.0 included.  There is no flag channel: a coordinate outside the domain (negative, fractional, NaN, 16384
+ * or more) gives an unspecified word, and the caller must not send such rows. */
 int v2e_events_pack64(const float *events, uint64_t *out, int64_t n, void *stream);
 int v2e_events_unpack64(const uint64_t *in, float *events, int64_t n, void *stream);
 
@@ -569,7 +572,11 @@ int v2e_events_unpack64(const uint64_t *in, float *events, int64_t n, void *stre
  * bits 62 (coordinate) and 63 (table too small), so that a receiver of the table sees them too; runs[1 + r] = float32 bits of t << 32 | index of the block's first event
  * (in order).  cap_runs: entries the run table holds besides runs[0] (a bound is sum over frames of max(iterations, 1));
  * scratch: device uint32 [v2e_events_pack32_scratch_words(n)], scratch[0] after the call: bit 0 a coordinate did not fit,
- * bit 1 the run table was too small (the caller then sends pack64).  unpack32 restores the float32 rows bit for bit. */
+ * bit 1 the run table was too small (the caller then sends pack64).  unpack32 restores the float32 rows bit for bit.
+ * A coordinate "does not fit" iff x is not an integer value in [0, 2048) or y is not one in [0, 1024): negative, fractional, NaN
+ * and infinite coordinates raise the flag like 2048 / 1024 and beyond (-0.0 is the integer 0 and is restored as +0.0).  The payload
+ * word of such a row is unspecified; the host refuses a flagged table.  Blocks split on the BITS of t: -0.0 and +0.0, or two NaNs
+ * with different payloads, are different time stamps; two NaNs with the same bits are one. */
 int v2e_events_pack32(const float *events, int64_t n, uint32_t *payload, uint64_t *runs, int64_t cap_runs,
                       uint32_t *scratch, void *stream);
 int64_t v2e_events_pack32_scratch_words(int64_t n);

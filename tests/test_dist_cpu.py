@@ -169,6 +169,21 @@ def test_wire_formats_round_trip_and_agree():
     assert torch.equal(unpack_events32(pl2, runs2).view(torch.int32), big.view(torch.int32))
     ev[7, 1] = 2048.0
     assert int(pack_events32(ev)[2][0]) != 0
+    # the flag's definition (include/v2e_amd.h): x is not an integer value in [0, 2048), or y is not one in [0, 1024).  One row at a
+    # time, in x and in y: negative, fractional, NaN and infinite coordinates are flagged like the ones that are too large
+    good = _rows_runs(200, 0, 1)
+    for col, size in ((1, 2048), (2, 1024)):
+        for v in (float(size - 1), 0.0, -0.0):
+            one = good.clone()
+            one[37, col] = v
+            pl1, runs1, fl1 = pack_events32(one)
+            assert int(fl1[0]) == 0 and int(runs1[0]) >> 62 == 0
+            assert torch.equal(unpack_events32(pl1, runs1), one)  # (== : -0.0 comes back as +0.0)
+        for v in (float(size), -1.0, -0.5, 0.5, size - 0.5, 1e9, -1e9, 3e38, float("inf"), float("-inf"), float("nan")):
+            one = good.clone()
+            one[37, col] = v
+            _, runs1, fl1 = pack_events32(one)
+            assert int(fl1[0]) == 1 and (int(runs1[0]) >> 62) & 3 == 1 and int(runs1[0]) & 0xFFFFFFFF == runs1.numel() - 1, (col, v)
 
 
 def test_clip_sharding_covers_all_clips():

@@ -123,9 +123,12 @@ __global__ __launch_bounds__(P32_BLOCK) void k_pack32_words(const float4 *__rest
     bool start = false;
     if (i < n) {
         const float4 e = ev[i];
-        const uint32_t x = (uint32_t)e.y, y = (uint32_t)e.z;
-        if (x >= 2048u || y >= 1024u) atomicOr(overflow, 1u); // does not fit 11 + 10 bits: the caller falls back to pack64
-        payload[i] = (x & 0x7FFu) | ((y & 0x3FFu) << 11) | (e.w > 0.f ? 1u << 21 : 0u);
+        // fits: x an integer value in [0, 2048), y one in [0, 1024).  The float comparisons come first: they refuse NaN, negative
+        // and huge values, which the conversion to an integer does not define
+        const bool fits = e.y >= 0.0f && e.y < 2048.0f && e.z >= 0.0f && e.z < 1024.0f && truncf(e.y) == e.y && truncf(e.z) == e.z;
+        const uint32_t x = fits ? (uint32_t)e.y : 0u, y = fits ? (uint32_t)e.z : 0u;
+        if (!fits) atomicOr(overflow, 1u); // does not fit 11 + 10 bits: the caller falls back to pack64
+        payload[i] = x | (y << 11) | (e.w > 0.f ? 1u << 21 : 0u);
         start = p32_starts_run(ev, i);
     }
     const unsigned long long b = __ballot(start);

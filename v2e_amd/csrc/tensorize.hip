@@ -18,6 +18,7 @@
 namespace {
 
 constexpr int LDS_BOUNDS_MAX = 4096;                       // explicit bounds staged in LDS up to this many entries (32 KB)
+constexpr int SCATTER_MAX_BLOCKS = 4096;                   // k_tensorize_scatter's grid: more rows than this holds take further trips
 constexpr unsigned int KEY_NEG_INF = 0x007fffffu;          // surf_key(-inf): what a pixel without an event holds
 constexpr double Q_ONE = 16777216.0;                       // 2^24: voxel weights are integers in units of 2^-24
 
@@ -227,7 +228,7 @@ int v2e_tensorize_scatter(const float *events, int64_t n, int H, int W, double t
     r.counters = (unsigned long long *)counters;
     const int64_t blocks = (n + 255) / 256;
     const size_t lds = (bounds && nk + 1 <= LDS_BOUNDS_MAX) ? (size_t)(nk + 1) * sizeof(double) : 0;
-    k_tensorize_scatter<<<(int)(blocks < 4096 ? blocks : 4096), 256, lds, (hipStream_t)stream>>>(r);
+    k_tensorize_scatter<<<(int)(blocks < SCATTER_MAX_BLOCKS ? blocks : SCATTER_MAX_BLOCKS), 256, lds, (hipStream_t)stream>>>(r);
     V2E_HIP(hipGetLastError());
     return 0;
 }

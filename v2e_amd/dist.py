@@ -97,9 +97,14 @@ def pack_events32(ev, payload=None, runs=None, cap_runs=None, scratch=None):
         return payload, runs, scratch
     e = ev.contiguous()
     tb = e[:, 0].contiguous().view(torch.int32)
-    x, y = e[:, 1].to(torch.int64), e[:, 2].to(torch.int64)
-    bad = bool(((x >= 2048) | (y >= 1024)).any()) if n else False
-    pl = ((x & 0x7FF) | ((y & 0x3FF) << 11) | ((e[:, 3] > 0).to(torch.int64) << 21)).to(torch.int32)
+    # as k_pack32_words: a row fits iff x is an integer value in [0, 2048) and y one in [0, 1024) (NaN, negative and fractional
+    # coordinates do not); a row that does not fit raises flag bit 0 and its payload word is unspecified
+    xf, yf = e[:, 1], e[:, 2]
+    fits = (xf >= 0) & (xf < 2048) & (yf >= 0) & (yf < 1024) & (xf == torch.trunc(xf)) & (yf == torch.trunc(yf))
+    bad = not bool(fits.all())
+    zero = torch.zeros((), dtype=torch.float32)
+    x, y = torch.where(fits, xf, zero).to(torch.int64), torch.where(fits, yf, zero).to(torch.int64)
+    pl = (x | (y << 11) | ((e[:, 3] > 0).to(torch.int64) << 21)).to(torch.int32)
     if n:
         start = torch.ones(n, dtype=torch.bool)
         start[1:] = tb[1:] != tb[:-1]
