@@ -901,6 +901,7 @@ static std::vector<unsigned char> graph_key(const v2e_emu *h, const v2e_emu_para
         push(&h->ch_K, sizeof(h->ch_K)); push(&h->ch_E, sizeof(h->ch_E)); push(&h->ch_fused, sizeof(h->ch_fused)); push(&h->ch_nD, sizeof(h->ch_nD));
         push(&h->ch_max_blocks, sizeof(h->ch_max_blocks));
         push(&r.ch_gM, sizeof(r.ch_gM)); push(&r.ch_tsold, sizeof(r.ch_tsold)); push(&h->ch_ck, sizeof(h->ch_ck)); push(&r.ch_cnt, sizeof(r.ch_cnt));
+        push(&r.ch_msk, sizeof(r.ch_msk));
     }
     return key;
 }

@@ -48,6 +48,7 @@ constexpr int CHAIN_K_MAX = 64; // (a lane per frame of a launch: rule threshold
 constexpr int CFRAME_THREADS = 1024;
 constexpr int CHAIN_SUB = 8; // frames of a sub-pass: their records are loaded together and decoded into registers at its start
 constexpr int CHAIN_MAX_ITERS = 1024; // k_cframe keeps one total per key in LDS
+static_assert(CCNT_MASK > (uint32_t)CHAIN_MAX_ITERS, "a saturated count word must still exceed every max_iters the chain accepts");
 // !FUSED: a launch's frames take very few distinct dt_over_tau bit patterns (times i / fps: two, now and then three), so what a record
 // decodes to beside its random part -- (1 - eps, eps * L), a function of the pixel byte and the frame's dt_over_tau -- is an entry of one
 // of a few 256-entry tables, built once per launch.  More distinct values than CHAIN_TAB_MAX: the launch decodes record by record.
@@ -160,8 +161,10 @@ __device__ __forceinline__ void store_event_wt(float4 *ev_clip, unsigned long lo
 }
 
 struct ChainArgs {
-    const void *const *frames_pp;     // FUSED: *frames_pp = frames of the run (a device variable the run's upload fills: the pointer is not
-                                      // baked into a captured graph), frame f at *frames_pp + f * frame_stride (bytes)
+    const void *const *frames_pp;     // *frames_pp = frames of the run (a device variable the run's upload fills: the pointer is not
+                                      // baked into a captured graph), frame f at *frames_pp + f * frame_stride (bytes).  Both chains
+                                      // read them until the run's last launch: FUSED builds its records from them, !FUSED takes
+                                      // the pixel byte from them (K * frame_stride < 4 GB: chain_fused_records)
     unsigned long long frame_stride;
     const uint32_t *fidx_base;        // FUSED: the run's first frame index
     const FrameCtl *ctl;              // [n_frames][n_clips]
@@ -169,10 +172,11 @@ struct ChainArgs {
     int pf0, pnf;                     // the previous launch's frames, to be validated (pnf = 0: nothing to validate)
     int D, n_clips, K, ngroups;
     int slot_f0, slot_pf0;            // f0 % D, pf0 % D from the host (the ring slot of frame fs + k is slot(fs) + k, wrapped: K <= D)
-    uint32_t *cnt;                    // [D][n_clips][npx_pad] count words, slot = frame % D
+    ccnt_t *cnt;                      // [D][n_clips][npx_pad] 16-bit count words (CCNT_*: the count saturates at 8191), slot = frame % D
     uint32_t *ruleM;                  // [D][n_clips] M of a frame finalised by the refractory rule, 0 otherwise
     float *tsold;                     // [D][n_clips][npx_pad] ts_mem before a rule-on frame's update, or nullptr
-    const uint2 *rec;                 // [D][n_clips][npx_pad] k_ahead's per-(frame, pixel) records (8 bytes: see AheadArgs)
+    const uint32_t *rec;              // !FUSED: [D][n_clips][npx_pad] k_ahead's per-(frame, pixel) records (4 bytes: see AheadArgs)
+    const uint4 *msk;                 // !FUSED: [D][n_clips][npx_pad / 64] k_ahead's per-(frame, wave) shot masks (see AheadArgs)
     uint32_t *gM_prev, *gM_cur;       // [K + 1][n_clips][K] rule-on maxima: row r = after r redo passes
     unsigned *bar_prev;               // [K][n_clips] rendezvous counters of the redo passes on the previous launch
     const void *base_in, *lp_in;      // state as the previous launch left it
@@ -209,7 +213,7 @@ struct ChainArgs {
 // One frame's state-independent quantities of a pixel as a 16-byte record (layout: see k_ahead), in two parts: the table part
 // (lin-log / eps, emulator_utils.py:18-45, 80-96) is a function of the pixel value and the frame's dt_over_tau alone; the random
 // part (leak step, :126-129, float32 left to right; shot decisions, :326-349) needs the Philox draws.  k_ahead computes the random
-// part and stores it with the pixel byte (8 bytes), k_chain rebuilds the table part from them with the same expressions.
+// part and stores it (4 bytes and two mask bits), k_chain rebuilds the table part from the frame's pixel byte with the same expressions.
 template <typename FT>
 __device__ __forceinline__ void frame_record_table(const KArgs &a, FT px, const float *s_lutL, const double *s_lutI, double dt_over_tau,
                                                    double &L, double &inten01, double &eps)
@@ -271,11 +275,11 @@ __device__ __forceinline__ uint4 make_frame_record(const KArgs &a, FT px, const 
     return pack_frame_record(eps, L, __float_as_uint(dl), sb);
 }
 
-// k_ahead's 8-byte record (see AheadArgs) of a uint8 frame -> the 16-byte record, with the frame's dt_over_tau: frame_record_table's
-// values, with both table entries read whatever the switches say (no branch between the table reads of a sub-pass boundary)
-__device__ __forceinline__ uint4 decode_frame_record(const KArgs &a, uint2 r8, const float *s_lutL, const double *s_lutI, double dt_over_tau)
+// k_ahead's record (the leak step's bits: see AheadArgs) and the pixel byte of a uint8 frame -> the 16-byte record without its shot
+// decisions (k_chain takes them from k_ahead's masks), with the frame's dt_over_tau: frame_record_table's values, with both table
+// entries read whatever the switches say (no branch between the table reads of a sub-pass boundary)
+__device__ __forceinline__ uint4 decode_frame_record(const KArgs &a, uint32_t dl_bits, int px, const float *s_lutL, const double *s_lutI, double dt_over_tau)
 {
-    const int px = (int)(r8.y & 0xFFu);
     const float tl = s_lutL[px];
     const double inten01 = s_lutI[px];
     const double L = a.log_input ? (double)px : (double)tl;
@@ -284,17 +288,22 @@ __device__ __forceinline__ uint4 decode_frame_record(const KArgs &a, uint2 r8, c
         eps = inten01 * dt_over_tau;
         if (eps > 1.0) eps = 1.0;
     }
-    return pack_frame_record(eps, L, r8.x, r8.y >> 30);
+    return pack_frame_record(eps, L, dl_bits, 0u);
 }
 
 // Everything about a frame that depends on no state, for all frames of a chain launch at once: lin-log of the pixel,
 // the low-pass coefficient eps (emulator_utils.py:80-96), the Philox draws, the leak step delta_leak
 // (emulator_utils.py:126-129, float32 left to right) and the shot-noise decisions (emulator_utils.py:326-349).  One thread per
 // (pixel, frame pair), so the draws of a pair cost one Philox call and the work runs at full occupancy beside the chain
-// instead of inside its one-wave-per-SIMD dependency chain.  Result: one 8-byte record per (frame, pixel) of uint8 frames
-//   .x     delta_leak (float32)
-//   .y     the pixel byte (bits 0-7), the shot ON / OFF decisions (bits 30, 31)
-// from which k_chain rebuilds, with the frame's dt_over_tau, the 16-byte record frame_body reads (make_frame_record)
+// instead of inside its one-wave-per-SIMD dependency chain.  Result, for uint8 frames:
+//   rec    one 4-byte record per (frame, pixel): delta_leak's float32 bits, all 32 of them (its sign and range depend on the jitter
+//          draw, the noise rate and the thresholds: no bit of it is free)
+//   msk    the shot decisions as ballots: per (frame, clip, wave of 64 pixels) one uint4 {ON low, ON high, OFF low, OFF high}, bit l =
+//          pixel 64 w + l (k_ahead's thread-to-pixel mapping is k_chain's; pixels beyond the frame are 0; a wave wholly in the padding
+//          is never written: the plane is zeroed when it is allocated)
+// -- 4.25 bytes per pixel and frame where round 7's record (leak step, pixel byte, two shot bits, 22 bits of padding) had 8.  The pixel
+// byte is not copied: k_chain reads it from the frame, which is resident for the whole run.  From these k_chain rebuilds, with the
+// frame's dt_over_tau, the 16-byte record frame_body reads (make_frame_record)
 //   .x .y  eps (float64, in [0,1]: top exponent bit and sign bit are free and carry the shot ON / OFF decisions)
 //   .z     lin-log value L (float32; the frame itself when it is log-encoded already)
 //   .w     delta_leak (float32)
@@ -307,13 +316,14 @@ struct AheadArgs {
     int f0, nf, D, n_clips;
     int slot0;  // f0 % D, from the host (a 64-bit remainder per frame and thread is ~60 instructions of a kernel that has 240)
     int ppt;    // frame pairs per thread (grid z = ceil(pairs / ppt))
-    uint2 *rec; // [D][n_clips][npx_pad]
+    uint32_t *rec; // [D][n_clips][npx_pad]
+    uint4 *msk;    // [D][n_clips][npx_pad / 64]
 };
 
 template <typename FT>
 __global__ __launch_bounds__(BLOCK) void k_ahead(KArgs a, AheadArgs aa)
 {
-    static_assert(sizeof(FT) == 1, "k_ahead's records carry the pixel byte: uint8 frames only");
+    static_assert(sizeof(FT) == 1, "k_chain decodes k_ahead's records with the pixel byte of the frame: uint8 frames only");
     __shared__ double s_lutI[256];
     const int tid = threadIdx.x;
     s_lutI[tid] = a.lut_I[tid];
@@ -352,8 +362,14 @@ __global__ __launch_bounds__(BLOCK) void k_ahead(KArgs a, AheadArgs aa)
             uint32_t sb;
             frame_record_rand(a, s_lutI[px], c->shot_base, (float)(c->t_frame - c->t_prev), lk, thp, ppre, npre, half ? r_even : r_odd,
                               half ? u_even : u_odd, dl, sb);
-            aa.rec[((uint32_t)sl * (uint32_t)aa.n_clips + (uint32_t)clip) * (uint32_t)a.npx_pad + (uint32_t)p] =
-                make_uint2(__float_as_uint(dl), (uint32_t)px | (sb << 30));
+            const uint32_t sc = (uint32_t)sl * (uint32_t)aa.n_clips + (uint32_t)clip;
+            aa.rec[sc * (uint32_t)a.npx_pad + (uint32_t)p] = __float_as_uint(dl);
+            // the wave's shot decisions (the frame test above is uniform; lanes beyond the frame have left and ballot as 0: lane 0 is
+            // here whenever any lane of the wave is)
+            const unsigned long long on = __ballot((sb & 1u) != 0u), off = __ballot((sb & 2u) != 0u);
+            if ((tid & (WAVE - 1)) == 0)
+                aa.msk[sc * (uint32_t)(a.npx_pad / WAVE) + (uint32_t)(p / WAVE)] =
+                    make_uint4((uint32_t)on, (uint32_t)(on >> 32), (uint32_t)off, (uint32_t)(off >> 32));
         }
     }
 }
@@ -377,8 +393,8 @@ template <typename R> __device__ __forceinline__ R floor_div_rcp(R a, R b, R rb)
 
 // FUSED = false: the frames' records come from k_ahead (small grids: the chain is one wave per SIMD and every instruction in it
 // is latency).  FUSED = true: the chain builds each record itself (large grids: the occupancy hides latencies, and the records'
-// 16 B per pixel and frame of extra HBM traffic -- 8 written, 8 read back -- would be what bounds the run).
-// FUSED = false: a sub-pass's CHAIN_SUB 8-byte records are decoded at the sub-pass boundary, all their table reads in flight at once,
+// 9.5 B per pixel and frame of extra HBM traffic -- 4.25 written, 5.25 read back -- would be what bounds the run).
+// FUSED = false: a sub-pass's CHAIN_SUB records (k_ahead's 4 bytes, the frame's pixel byte, the wave's shot masks) are decoded at the sub-pass boundary, all their table reads in flight at once,
 // into what frame_body consumes (1 - eps, eps * L, leak step, shot bits: registers), so that a frame starts with the IIR.
 // ALLON: instantiation for runs with a photoreceptor cutoff, leak, shot noise AND a refractory period (the v2e CLI defaults,
 // i.e. the benchmark): the per-frame tests of those run-time switches -- a scalar compare and a branch each, in a loop whose
@@ -418,6 +434,7 @@ void k_chain(KArgs a_in, ChainArgs ca)
     if (!FUSED) {
         tab_L = a.lut_L[tid];
         tab_I = a.lut_I[tid];
+        frames = (const char *)*ca.frames_pp;
     }
     if (FUSED) {
         fbase = *ca.fidx_base;
@@ -446,28 +463,45 @@ void k_chain(KArgs a_in, ChainArgs ca)
         const uint32_t slot_px = (uint32_t)((size_t)ca.n_clips * a.npx_pad); // pixels of one ring slot
         const __amdgpu_buffer_rsrc_t rec_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)ca.rec, 0, -1, 0x00020000);
         const __amdgpu_buffer_rsrc_t cnt_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)ca.cnt, 0, -1, 0x00020000);
-        auto load_rec = [&](const int sl) __attribute__((always_inline)) -> uint2 {
-            const v2e_u2 v = __builtin_amdgcn_raw_buffer_load_b64(rec_rsrc, (int)(lane_px * 8u), (int)((uint32_t)sl * slot_px * 8u), 0);
-            return make_uint2(v.x, v.y);
-        };
-        // the 16-byte record of frame k of a pass from k_ahead's 8-byte one, with the frame's dt_over_tau (dtau_v: lane k = frame k of the
-        // pass) -- and a ZERO record for a lane beyond the frame: with its zero state it gives no events (the frame loop carries no
-        // per-lane validity test; a zero 8-byte record does not decode to zero: lut_I[0] > 0)
-        auto decode_rec = [&](const uint2 r8, const double dtau_v, const int k) __attribute__((always_inline)) -> uint4 {
-            const double dtau = a.has_cutoff ? lane_value_d(dtau_v, k) : 0.0;
-            const uint4 r = decode_frame_record(a, r8, s_lutL, s_lutI, dtau);
-            return valid ? r : make_uint4(0u, 0u, 0u, 0u);
-        };
-        uint2 st[CHAIN_SUB]; // !FUSED: the records of a pass's first sub-pass, as stage() loaded them
-        auto stage = [&](const int sl0, const int fn) __attribute__((always_inline)) { // the first CHAIN_SUB frames of a pass (sl0: the first one's slot)
-            if (FUSED) return;
+        const __amdgpu_buffer_rsrc_t msk_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)ca.msk, 0, -1, 0x00020000);
+        const uint32_t wave_ix = lane_px / WAVE, slot_waves = slot_px / WAVE; // this wave's entry of a slot's mask plane; entries per slot
+        const bool wave_live = p - lane < a.npx;                               // the wave has a pixel of the frame: k_ahead wrote its masks
+        // What a sub-pass loads per frame: k_ahead's 4-byte record, the pixel byte -- from the frame itself, through a buffer resource
+        // based at the pass's first frame of this clip, the frame's offset in the scalar offset (32 bits: chain_fused_records) -- and
+        // the frame's shot masks of this wave, one frame per lane.  A lane beyond the frame loads nothing: frame rows are npx long, not
+        // npx_pad, so behind the run's last frame there is nothing to read; its byte is 0 and its table entry inv_px's.
+        struct SubRec { uint32_t dl[CHAIN_SUB], px[CHAIN_SUB]; v2e_u4 m; };
+        // frames [k0, k0 + cn) of the pass whose first frame is f_first (k0's ring slot: sl0); cn <= 0: none
+        auto load_sub = [&](SubRec &s, const int f_first, const int k0, const int sl0, const int cn) __attribute__((always_inline)) {
+            const __amdgpu_buffer_rsrc_t px_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+                (void *)(frames + (size_t)f_first * ca.frame_stride + (size_t)clip * a.npx * sizeof(FT)), 0, -1, 0x00020000);
             int sl = sl0;
 #pragma unroll
             for (int j = 0; j < CHAIN_SUB; ++j) {
-                st[j] = make_uint2(0u, 0u);
-                if (j < fn && valid) st[j] = load_rec(sl);
+                s.dl[j] = s.px[j] = 0u;
+                if (j < cn && valid) {
+                    s.dl[j] = __builtin_amdgcn_raw_buffer_load_b32(rec_rsrc, (int)(lane_px * 4u), (int)((uint32_t)sl * slot_px * 4u), 0);
+                    s.px[j] = __builtin_amdgcn_raw_buffer_load_b8(px_rsrc, p, (int)((uint32_t)(k0 + j) * (uint32_t)ca.frame_stride), 0);
+                }
                 if (++sl == ca.D) sl = 0;
             }
+            s.m = v2e_u4{0u, 0u, 0u, 0u};
+            int slm = sl0 + lane; // lane j: frame k0 + j (cn <= CHAIN_SUB <= D: one wrap)
+            if (slm >= ca.D) slm -= ca.D;
+            if (wave_live && lane < cn) s.m = __builtin_amdgcn_raw_buffer_load_b128(msk_rsrc, (int)(((uint32_t)slm * slot_waves + wave_ix) * 16u), 0, 0);
+        };
+        // the 16-byte record of frame k of a pass from k_ahead's record and the pixel byte, with the frame's dt_over_tau (dtau_v: lane k =
+        // frame k of the pass) -- and a ZERO record for a lane beyond the frame: with its zero state it gives no events (the frame loop
+        // carries no per-lane validity test; a zero record and byte do not decode to zero: lut_I[0] > 0)
+        auto decode_rec = [&](const uint32_t dl_bits, const uint32_t px, const double dtau_v, const int k) __attribute__((always_inline)) -> uint4 {
+            const double dtau = a.has_cutoff ? lane_value_d(dtau_v, k) : 0.0;
+            const uint4 r = decode_frame_record(a, dl_bits, (int)px, s_lutL, s_lutI, dtau);
+            return valid ? r : make_uint4(0u, 0u, 0u, 0u);
+        };
+        SubRec st; // !FUSED: a pass's first sub-pass, as stage() loaded it
+        auto stage = [&](const int f_first, const int k0, const int sl0, const int fn) __attribute__((always_inline)) { // frames [k0, k0 + min(fn, CHAIN_SUB)) of a pass
+            if (FUSED) return;
+            load_sub(st, f_first, k0, sl0, min(fn, CHAIN_SUB));
         };
         // !FUSED: what frame_body consumes of the sub-pass's frame j, decoded from k_ahead's record at the sub-pass boundary: 1 - eps
         // and eps * L (the two state-free operands of the IIR, emulator_utils.py:96; L itself where there is no cutoff), the leak
@@ -480,29 +514,41 @@ void k_chain(KArgs a_in, ChainArgs ca)
         // records are zero: never loaded) reads entry 256 of the table, (1, 0): what the zero record decodes to below.
         bool use_tab = false;
         const uint32_t inv_px = valid ? 0u : 256u;
-        auto decode_sub = [&](const uint2 *r, const int kb, const double dtau_v, const uint32_t tix_v) __attribute__((always_inline)) {
+        auto decode_sub = [&](const SubRec &s, const int kb, const double dtau_v, const uint32_t tix_v) __attribute__((always_inline)) {
             if (FUSED) return;
+            // The shot decisions behind ONE wave-uniform test per sub-pass: no mask of its frames has a bit (lane j of s.m: frame j;
+            // the usual case: a few shot events per frame in the whole array) and nothing is read.  Otherwise a frame's masks come by lane
+            // reads, and a lane takes its own bit of each.
+#pragma unroll
+            for (int j = 0; j < CHAIN_SUB; ++j) dq_sb[j] = 0u;
+            if (__ballot((s.m.x | s.m.y | s.m.z | s.m.w) != 0u) != 0ull) {
+#pragma unroll
+                for (int j = 0; j < CHAIN_SUB; ++j) {
+                    const uint32_t on_lo = (uint32_t)__builtin_amdgcn_readlane((int)s.m.x, j), on_hi = (uint32_t)__builtin_amdgcn_readlane((int)s.m.y, j);
+                    const uint32_t off_lo = (uint32_t)__builtin_amdgcn_readlane((int)s.m.z, j), off_hi = (uint32_t)__builtin_amdgcn_readlane((int)s.m.w, j);
+                    const uint32_t on = lane < 32 ? on_lo : on_hi, off = lane < 32 ? off_lo : off_hi;
+                    dq_sb[j] = (((on >> (lane & 31)) & 1u) ? CCNT_SHOT_ON : 0u) | (((off >> (lane & 31)) & 1u) ? CCNT_SHOT_OFF : 0u);
+                }
+            }
             if (use_tab) {
 #pragma unroll
                 for (int j = 0; j < CHAIN_SUB; ++j) {
                     const uint32_t toff = (uint32_t)__builtin_amdgcn_readlane((int)tix_v, (kb + j) & (WAVE - 1));
-                    const double2 e = s_tab[toff + ((r[j].y & 0xFFu) | inv_px)];
+                    const double2 e = s_tab[toff + (s.px[j] | inv_px)];
                     dq_om[j] = e.x;
                     dq_el[j] = e.y;
-                    dq_dl[j] = __uint_as_float(r[j].x);
-                    dq_sb[j] = (r[j].y >> 5) & (CNT_SHOT_ON | CNT_SHOT_OFF);
+                    dq_dl[j] = __uint_as_float(s.dl[j]);
                 }
                 return;
             }
 #pragma unroll
             for (int j = 0; j < CHAIN_SUB; ++j) { // (a frame beyond the pass decodes to values nothing reads)
-                const uint4 rc = decode_rec(r[j], dtau_v, (kb + j) & (WAVE - 1));
+                const uint4 rc = decode_rec(s.dl[j], s.px[j], dtau_v, (kb + j) & (WAVE - 1));
                 const double eps = __longlong_as_double((long long)(((unsigned long long)(rc.y & 0x3FFFFFFFu) << 32) | rc.x));
                 const double L = (double)__uint_as_float(rc.z);
                 dq_om[j] = 1.0 - eps;
                 dq_el[j] = a.has_cutoff ? eps * L : L;
                 dq_dl[j] = __uint_as_float(rc.w);
-                dq_sb[j] = (rc.y >> 5) & (CNT_SHOT_ON | CNT_SHOT_OFF);
             }
         };
         auto fill_scalars = [&](const int fs, const int fn) __attribute__((always_inline)) { // FUSED: the pass's frame scalars
@@ -555,7 +601,7 @@ void k_chain(KArgs a_in, ChainArgs ca)
             dtime_r = (float)(c->t_frame - c->t_prev);
         }
         if (FUSED && valid && a.do_leak) nr = a.noise_rate[sp];
-        stage(ca.slot_f0, ca.nf); // this launch's own frames (almost always the only pass)
+        stage(ca.f0, 0, ca.slot_f0, ca.nf); // this launch's own frames (almost always the only pass)
         if (FUSED)
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(b), "+v"(lp), "+v"(tsm), "+v"(thp), "+v"(thn), "+v"(gM_v), "+v"(mon_own), "+v"(mon_prev) : : "memory");
         else
@@ -680,7 +726,7 @@ void k_chain(KArgs a_in, ChainArgs ca)
             const uint32_t tix_v = own ? tix_own : tix_prev;
             if (redone) { // a redo pass, or the own pass after one: its inputs replace what the prologue staged
                 fill_scalars(fs, fn);
-                stage(wrap_slot(fs_slot + c0), fn - c0);
+                stage(fs, c0, wrap_slot(fs_slot + c0), fn - c0);
             }
             const uint32_t mon_v = own ? mon_own : mon_prev;
             // the smallest rule threshold of the pass's frames (lanes beyond them hold 0xFFFFFFFF): the light body's coarse speculation test
@@ -731,7 +777,7 @@ void k_chain(KArgs a_in, ChainArgs ca)
                     if (a.has_cutoff) lpn = (R)((1.0 - eps) * (double)lp + eps * L);
                     else lpn = (R)L;
                     dl = __uint_as_float(rc.w);
-                    sbw = (rc.y >> 5) & (CNT_SHOT_ON | CNT_SHOT_OFF);
+                    sbw = (rc.y >> 16) & (CCNT_SHOT_ON | CCNT_SHOT_OFF);
                 } else {
                     if (a.has_cutoff) lpn = (R)(dq_om[js] * (double)lp + dq_el[js]);
                     else lpn = (R)dq_el[js];
@@ -762,12 +808,13 @@ void k_chain(KArgs a_in, ChainArgs ca)
                     mag = q > 0 ? q : 0;
                 }
                 if (FUSED && !valid) mag = 0; // (k_ahead's records of a pixel beyond the frame are zero: no events by themselves)
-                // count word: count | sign (events only) | the record's shot decisions
-                uint32_t cw = ((uint32_t)mag & CNT_MASK) | ((mag > 0 && neg) ? CNT_NEG : 0u);
+                // count word: count (saturated: such a frame is beyond max_iters and refused) | sign (events only) | the record's shot
+                // decisions; the state below advances from mag itself
+                uint32_t cw = min((uint32_t)mag, CCNT_MASK) | ((mag > 0 && neg) ? CCNT_NEG : 0u);
                 if (a.do_shot) cw |= sbw;
                 if (FUSED && !valid) cw = 0u;
                 if (FUSED) {
-                    if (valid) WT_STORE(&ca.cnt[((size_t)wrap_slot(fs_slot + k) * ca.n_clips + clip) * a.npx_pad + p], cw);
+                    if (valid) WT_STORE(&ca.cnt[((size_t)wrap_slot(fs_slot + k) * ca.n_clips + clip) * a.npx_pad + p], (ccnt_t)cw);
                 }
                 const int magv = mag;
                 magq = (uint32_t)magv;
@@ -830,16 +877,11 @@ void k_chain(KArgs a_in, ChainArgs ca)
             // records of the pass's frames [kn, kn + CHAIN_SUB) into registers (in flight while the frames before them compute)
             // (two sub-passes ahead instead of one -- the registers the 8-byte records freed -- measured slower:
             //  profiles/r07_emulator_experiments.txt item 3)
-            uint2 nx[CHAIN_SUB];
+            SubRec nx;
             auto fetch_next = [&](const int kn) __attribute__((always_inline)) {
+                if (FUSED) return;
                 const int cn = min(CHAIN_SUB, fn - kn); // <= 0: none
-                int sl = cn > 0 ? wrap_slot(fs_slot + kn) : 0;
-#pragma unroll
-                for (int j = 0; j < CHAIN_SUB; ++j) {
-                    nx[j] = make_uint2(0u, 0u);
-                    if (!FUSED && valid && j < cn) nx[j] = load_rec(sl);
-                    if (++sl == ca.D) sl = 0;
-                }
+                load_sub(nx, fs, kn, cn > 0 ? wrap_slot(fs_slot + kn) : 0, cn);
             };
             decode_sub(st, c0, dtau_v, tix_v);
             fetch_next(c0 + CHAIN_SUB);
@@ -915,7 +957,7 @@ void k_chain(KArgs a_in, ChainArgs ca)
 #pragma unroll
                         for (int j = 0; j < CHAIN_SUB; ++j) { // the sub-pass's count words
                             if (k0 + j < kend)
-                                __builtin_amdgcn_raw_buffer_store_b32(cwq[j], cnt_rsrc, (int)(lane_px * 4u), (int)((uint32_t)sl * slot_px * 4u), 17); // sc0 sc1: written through, as WT_STORE
+                                __builtin_amdgcn_raw_buffer_store_b16((short)cwq[j], cnt_rsrc, (int)(lane_px * (uint32_t)sizeof(ccnt_t)), (int)((uint32_t)sl * slot_px * (uint32_t)sizeof(ccnt_t)), 17); // sc0 sc1: written through, as WT_STORE
                             if (++sl == ca.D) sl = 0;
                         }
                     }
@@ -966,7 +1008,7 @@ struct CEmitArgs {
     const uint32_t *fidx_base;
     int f0, nE, D, n_clips, nwp, nwaves, E;
     int slot0;           // f0 % D, from the host
-    const uint32_t *cnt;
+    const ccnt_t *cnt;   // the chain's ring of 16-bit count words (CCNT_*)
     const uint32_t *ruleM; // [D][n_clips] (refractory runs) or nullptr
     uint16_t *wmax;      // [E][n_clips][nwp] per-group max count (k_ctot); nwaves = groups of 256 pixels, nwp = that padded to 16
     uint16_t *wtot;      // [E][n_clips][nkeys_cap][nwp] per-group key totals, <= 256 each (k_ctot)
@@ -1051,12 +1093,12 @@ __global__ __launch_bounds__(BLOCK) void k_ctot(KArgs a, CEmitArgs ea)
 #pragma unroll
         for (int j = 0; j < GPX; ++j) {
             const uint32_t cw = cwq[q][j];
-            magv[j] = (int)(cw & CNT_MASK);
-            neg[j] = (cw & CNT_NEG) != 0;
+            magv[j] = (int)(cw & CCNT_MASK);
+            neg[j] = (cw & CCNT_NEG) != 0;
             negb[j] = __ballot(neg[j]);
             mmax = max(mmax, magv[j]);
-            sob[j] = __ballot((cw & CNT_SHOT_ON) != 0);
-            sfb[j] = __ballot((cw & CNT_SHOT_OFF) != 0);
+            sob[j] = __ballot((cw & CCNT_SHOT_ON) != 0);
+            sfb[j] = __ballot((cw & CCNT_SHOT_OFF) != 0);
             son += (uint32_t)__popcll(sob[j]);
             soff += (uint32_t)__popcll(sfb[j]);
         }
@@ -1511,8 +1553,8 @@ __global__ __launch_bounds__(BLOCK) void k_cemit(KArgs a, CEmitArgs ea)
     unsigned long long any_shot = 0ull;
 #pragma unroll
     for (int j = 0; j < GPX; ++j) {
-        so[j] = __ballot((cw[j] & CNT_SHOT_ON) != 0);
-        sf[j] = __ballot((cw[j] & CNT_SHOT_OFF) != 0);
+        so[j] = __ballot((cw[j] & CCNT_SHOT_ON) != 0);
+        sf[j] = __ballot((cw[j] & CCNT_SHOT_OFF) != 0);
         any_shot |= so[j] | sf[j];
     }
     if (wmw == 0 && any_shot == 0ull) return; // nothing of this group in the frame
@@ -1525,8 +1567,8 @@ __global__ __launch_bounds__(BLOCK) void k_cemit(KArgs a, CEmitArgs ea)
     float tsm[GPX];
 #pragma unroll
     for (int j = 0; j < GPX; ++j) {
-        mag[j] = (int)(cw[j] & CNT_MASK);
-        neg[j] = (cw[j] & CNT_NEG) != 0;
+        mag[j] = (int)(cw[j] & CCNT_MASK);
+        neg[j] = (cw[j] & CCNT_NEG) != 0;
         negb[j] = __ballot(neg[j]);
         tsm[j] = 0.f;
     }
@@ -1665,8 +1707,8 @@ __global__ __launch_bounds__(BLOCK) void k_cemit(KArgs a, CEmitArgs ea)
             if ((so[j] | sf[j]) != 0ull) {
                 float fx, fy;
                 pixel_xy((uint32_t)(p0 + j * WAVE), fx, fy);
-                if (cw[j] & CNT_SHOT_ON) store_row(son_off + (uint32_t)__popcll(so[j] & lt), tl, fx, fy, 1.0f);
-                if (cw[j] & CNT_SHOT_OFF) store_row(soff_off + (uint32_t)__popcll(sf[j] & lt), tl, fx, fy, -1.0f);
+                if (cw[j] & CCNT_SHOT_ON) store_row(son_off + (uint32_t)__popcll(so[j] & lt), tl, fx, fy, 1.0f);
+                if (cw[j] & CCNT_SHOT_OFF) store_row(soff_off + (uint32_t)__popcll(sf[j] & lt), tl, fx, fy, -1.0f);
                 son_off += (uint32_t)__popcll(so[j]);
                 soff_off += (uint32_t)__popcll(sf[j]);
             }

@@ -70,8 +70,10 @@ static bool chain_fused_records(const v2e_emu *h, int dtype, int nD)
 {
     if (dtype != V2E_DT_U8) return true; // k_ahead's record path is instantiated for uint8 frames only
     // k_chain reads k_ahead's records and writes the count words through buffer resources (32-bit offsets): the record ring of
-    // nD batches of up to 64 frames must stay below 4 GB (1280x720: 1.4 GB with three batches; beyond that the chain builds the records)
-    if ((size_t)nD * 64 * h->n_clips * h->npx_pad * sizeof(uint2) >= (1ull << 32)) return true;
+    // nD batches of up to 64 frames must stay below 4 GB (beyond that the chain builds the records).  The same bound covers the
+    // smaller planes (count words, shot masks) and the frames of one launch, which the chain reads the pixel bytes from at
+    // k * frame_stride, k < K <= 64, frame_stride = n_clips * npx bytes.
+    if ((size_t)nD * 64 * h->n_clips * h->npx_pad * sizeof(uint32_t) >= (1ull << 32)) return true;
     const char *fe = getenv("V2E_AMD_CHAIN_FUSED"); // read per call: tests switch it per emulator instance
     const int fused_env = fe ? atoi(fe) : -1;
     return fused_env >= 0 ? fused_env != 0 : !chain_small_grid(h);
@@ -198,7 +200,7 @@ static int chain_alloc(v2e_emu *h, const v2e_emu_params *p, int dtype, int n_fra
     if (!chain_small_grid(h)) {
         if (h->ch_long_batches < 0) { // decided once per handle (the answer must not change with what the handle itself allocates)
             size_t free_b = 0, total_b = 0;
-            const size_t ring = (size_t)3 * 64 * h->n_clips * h->npx_pad * (sizeof(uint32_t) + sizeof(float) + sizeof(uint2));
+            const size_t ring = (size_t)3 * 64 * h->n_clips * h->npx_pad * (sizeof(ccnt_t) + sizeof(float) + sizeof(uint32_t));
             h->ch_long_batches = (hipMemGetInfo(&free_b, &total_b) == hipSuccess && ring <= free_b / 8) ? 1 : 0;
         }
         // (64 clips of 346x260 have 2 048 (frame, clip) pairs in a 32-frame batch already: 11.64 Gev/s with 32 frames, 11.37 with 64)
@@ -232,7 +234,7 @@ static int chain_alloc(v2e_emu *h, const v2e_emu_params *p, int dtype, int n_fra
     const size_t nc = (size_t)h->n_clips;
     RunScratch &r = h->cur();
     if (!r.ch_cnt) {
-        V2E_HIP(hipMalloc(&r.ch_cnt, sizeof(uint32_t) * h->ch_D * nc * h->npx_pad));
+        V2E_HIP(hipMalloc(&r.ch_cnt, sizeof(ccnt_t) * h->ch_D * nc * h->npx_pad));
         V2E_HIP(hipMalloc(&r.ch_ruleM, sizeof(uint32_t) * h->ch_D * nc));
         V2E_HIP(hipMemset(r.ch_ruleM, 0, sizeof(uint32_t) * h->ch_D * nc));
         // three sets of emission tables in rotation: the tables of batches b + 1, b + 2 are built while k_cemit(b) reads its own
@@ -253,8 +255,11 @@ static int chain_alloc(v2e_emu *h, const v2e_emu_params *p, int dtype, int n_fra
             V2E_HIP(hipMalloc(&r.ch_cpre16, 3 * sizeof(uint32_t) * E * nc * h->nkeys_cap * (h->ch_nwp / 16)));
         }
         if (!fused) { // (zero once: k_ahead never writes a slot's padding [npx, npx_pad), and k_chain's lanes beyond the frame read it)
-            V2E_HIP(hipMalloc(&r.ch_rec, sizeof(uint2) * (size_t)h->ch_D * nc * h->npx_pad));
-            V2E_HIP(hipMemset(r.ch_rec, 0, sizeof(uint2) * (size_t)h->ch_D * nc * h->npx_pad));
+            V2E_HIP(hipMalloc(&r.ch_rec, sizeof(uint32_t) * (size_t)h->ch_D * nc * h->npx_pad));
+            V2E_HIP(hipMemset(r.ch_rec, 0, sizeof(uint32_t) * (size_t)h->ch_D * nc * h->npx_pad));
+            // (and the shot masks of a wave wholly in the padding, which k_ahead never writes and k_chain never reads, stay zero)
+            V2E_HIP(hipMalloc(&r.ch_msk, sizeof(uint4) * (size_t)h->ch_D * nc * (h->npx_pad / WAVE)));
+            V2E_HIP(hipMemset(r.ch_msk, 0, sizeof(uint4) * (size_t)h->ch_D * nc * (h->npx_pad / WAVE)));
         }
         // The fills above are ordered on the DEFAULT stream only, and a pipelined run's head (its k_ahead records, its tables) goes out on
         // streams of the handle that do not wait for it: enqueued behind a run still executing on the default stream, the record ring's
@@ -473,7 +478,7 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
             aa.frames_pp = r.run_frames; aa.frame_stride = (unsigned long long)NC * h->npx * esz;
             aa.ctl = r.run_ctl; aa.fidx_base = r.run_fidx;
             aa.f0 = f0; aa.nf = f1 - f0; aa.D = D; aa.n_clips = NC; aa.slot0 = f0 % D;
-            aa.rec = r.ch_rec;
+            aa.rec = r.ch_rec; aa.msk = r.ch_msk;
             // frame pairs per thread: a thread's set-up (thresholds, two divisions, the seed's ten Philox round keys) is paid once per
             // thread, so a thread takes several pairs -- as many as leave ~4 workgroups per CU (346x260, 64 frames: 3 z-blocks of 11 pairs;
             // round 6, A/B x 3 in one session: 1 pair 683-689 us per step, 4: 668-676, 11: 665-670, 16: 663-671; k_ahead's instructions
@@ -536,7 +541,7 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
         ca.D = D; ca.n_clips = NC; ca.K = K; ca.ngroups = h->ngroups;
         ca.slot_f0 = pl.f0 % D; ca.slot_pf0 = pl.pf0 % D;
         ca.cnt = r.ch_cnt; ca.ruleM = r.ch_ruleM; ca.tsold = has_refr ? r.ch_tsold : nullptr;
-        ca.rec = r.ch_rec;
+        ca.rec = r.ch_rec; ca.msk = r.ch_msk;
         if (has_refr) {
             ca.gM_cur = r.ch_gM + (size_t)L * (K + 1) * NC * K;
             ca.gM_prev = r.ch_gM + (size_t)(L > 0 ? L - 1 : 0) * (K + 1) * NC * K;

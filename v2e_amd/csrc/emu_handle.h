@@ -12,8 +12,9 @@ struct RunScratch {
     // sized by the chain configuration (K, E, keys; v2e_emu::ch_*)
     uint32_t *ch_gM = nullptr;      // [ch_launch_cap][ch_K + 1][n_clips][ch_K]
     unsigned *ch_bar = nullptr;     // [ch_launch_cap][2 ch_K][n_clips]: one counter per rendezvous of a launch (passes + lock-step frames)
-    uint2 *ch_rec = nullptr;        // [ch_D][n_clips][npx_pad] k_ahead's per-(frame, pixel) records (8 bytes: see AheadArgs)
-    uint32_t *ch_cnt = nullptr;     // [ch_D][n_clips][npx_pad]
+    uint32_t *ch_rec = nullptr;     // [ch_D][n_clips][npx_pad] k_ahead's per-(frame, pixel) records (4 bytes: see AheadArgs)
+    uint4 *ch_msk = nullptr;        // [ch_D][n_clips][npx_pad / 64] k_ahead's per-(frame, wave) shot masks (see AheadArgs)
+    ccnt_t *ch_cnt = nullptr;       // [ch_D][n_clips][npx_pad] the chain's 16-bit count words (CCNT_*, emu_kernels.h)
     uint32_t *ch_ruleM = nullptr;   // [ch_D][n_clips]
     float *ch_tsold = nullptr;      // [ch_D][n_clips][npx_pad] (refractory runs)
     uint16_t *ch_wmax = nullptr;    // [3][ch_E][n_clips][ch_nwp]
@@ -27,7 +28,7 @@ struct RunScratch {
     template <typename T> static void drop(T *&b) { hipFree((void *)b); b = nullptr; }
     void free_chain()
     {
-        drop(ch_gM); drop(ch_bar); drop(ch_rec); drop(ch_cnt); drop(ch_ruleM); drop(ch_tsold); drop(ch_wmax); drop(ch_wtot);
+        drop(ch_gM); drop(ch_bar); drop(ch_rec); drop(ch_msk); drop(ch_cnt); drop(ch_ruleM); drop(ch_tsold); drop(ch_wmax); drop(ch_wtot);
         drop(ch_cf); drop(ch_cdone); drop(ch_cT); drop(ch_ckbase); drop(ch_cperm); drop(ch_cpre); drop(ch_cmask); drop(ch_cpre16);
     }
     void free_all()

@@ -13,6 +13,14 @@ constexpr uint32_t CNT_MASK = 0x00FFFFFFu;
 constexpr uint32_t CNT_NEG = 1u << 24;
 constexpr uint32_t CNT_SHOT_ON = 1u << 25;
 constexpr uint32_t CNT_SHOT_OFF = 1u << 26;
+// The chain's ring (RunScratch::ch_cnt) keeps a 16-bit word per (frame, pixel) instead: its count saturates at CCNT_MASK.  A frame
+// with a pixel beyond max_iters <= CHAIN_MAX_ITERS (emu_chain.h) is refused, a saturated one with it; the chain advances the pixel
+// state from the count in its registers, never from the word.
+typedef uint16_t ccnt_t;
+constexpr uint32_t CCNT_MASK = 0x1FFFu;
+constexpr uint32_t CCNT_NEG = 1u << 13;
+constexpr uint32_t CCNT_SHOT_ON = 1u << 14;
+constexpr uint32_t CCNT_SHOT_OFF = 1u << 15;
 
 struct KArgs {
     int W, npx, nwaves, nkeys_cap, max_iters;

@@ -374,6 +374,8 @@ class EventEmulator(object):
         # buffer set -> weakref of the run that last used it; handles of runs enqueued before the reset are no longer collected on
         # the caller's behalf
         self._async_slots = {}
+        # buffer set -> the device frames of the run that last used it (kept across a reset: such a run may still be executing)
+        self._run_frames = getattr(self, "_run_frames", {})
         self.num_events_total = 0
         self.num_events_on = 0
         self.num_events_off = 0
@@ -869,6 +871,10 @@ class EventEmulator(object):
             probe_dev = eng.probe_buffer(nrun, len(probe_idx), which)
             eng.set_probes(probe_idx, probe_dev)
         eng.run(P, frames_dev[start:], t_prev, t_frames[start:], self.frame_counter, ev, recs, use_graph=ug)
+        # Both chains read the frames until the run's last launch (the one on k_ahead's records takes the pixel bytes from them), and
+        # k_ahead reads them on a stream of the library's own: they stay referenced until this buffer set's next run is enqueued,
+        # behind this one, whether or not the caller keeps its tensor or the handle.
+        self._run_frames[which] = frames_dev
         ticket = None
         if ug & _capi.RUN_PIPELINED:
             # the library may have enqueued the run in pieces on streams of its own: result() waits for them on the host; a device-side
