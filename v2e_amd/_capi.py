@@ -244,6 +244,15 @@ def lib():
     return l
 
 
+def require_gpu(name, have=None):
+    """V2EAmdError in the words of class `name` unless there is a GPU (have: the caller's own test, where it has one)."""
+    if have is None:
+        import torch  # (not at module level: the binding itself loads without torch)
+        have = torch.cuda.is_available()
+    if not have:
+        raise V2EAmdError("v2e_amd.%s needs a ROCm GPU; there is no CPU fallback" % name)
+
+
 def ptr(t):
     """The device (or pinned host) address of a tensor as the void pointer the entry points take; None stays None (NULL)."""
     return None if t is None else C.c_void_p(t.data_ptr())

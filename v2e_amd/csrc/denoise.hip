@@ -11,7 +11,7 @@
 //
 // The filter is serial only through "the latest earlier row at pixel q".  k_denoise_keys gives row i the key pixel << 32 | i
 // (a bad row KEY_BAD, above every other); the host sorts the keys; k_denoise_segments finds each pixel's stretch of the sorted
-// keys; in k_denoise_ages that lookup is a binary search of q's stretch for the largest row index below i.  Every row is then
+// keys; in k_denoise_ages that lookup is rowkeys.h's latest_before, a binary search of q's stretch.  Every row is then
 // independent of the others, every sum is an integer atomic (LDS int32 per workgroup, flushed with 64-bit global atomics), and
 // the result does not depend on how threads are scheduled or how a clip is cut into calls.
 #include "common.h"
@@ -21,7 +21,7 @@ namespace {
 
 constexpr int MAX_TAUS = 256;
 constexpr int LDS_LABEL_BOUNDS_MAX = 2048;                  // label bounds staged in LDS up to this many entries (16 KB)
-constexpr int AGES_MAX_BLOCKS = 2048;                       // (KEY_BAD and row_pixel: rowkeys.h)
+constexpr int AGES_MAX_BLOCKS = 2048;                       // (keys, stretches and the lookup in them: rowkeys.h)
 
 __global__ __launch_bounds__(256) void k_denoise_keys(const float4 *__restrict__ ev, long long n, int H, int W, long long *__restrict__ keys,
                                                       unsigned char *__restrict__ keep)
@@ -40,12 +40,7 @@ __global__ __launch_bounds__(256) void k_denoise_segments(const long long *__res
 {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     if (p > npx) return;
-    const long long key = p << 32;
-    int a = 0, z = n;
-    while (a < z) {
-        const int mid = a + ((z - a) >> 1);
-        if (sorted[mid] < key) a = mid + 1; else z = mid;
-    }
+    const int a = count_lt<long long>(sorted, n, p << 32);
     seg[p] = a;
     if (p == npx && counters) {
         if (a) atomicAdd(&counters[0], (unsigned long long)a);
@@ -95,15 +90,12 @@ __global__ __launch_bounds__(256) void k_denoise_ages(AgesArgs r)
     __syncthreads();
     const long long *lb = lb_lds ? s_lb : r.lbounds;
     const int W = r.W, H = r.H;
-    const int n_seg = r.seg[(long long)H * W], n_valid = n_seg < r.n ? n_seg : r.n; // (no read past the pass's keys, whatever seg holds)
+    const int n_valid = valid_keys(r.seg, H, W, r.n);
 
     for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < n_valid; j += (long long)gridDim.x * 256) {
-        const long long key = r.sorted[j];
-        const unsigned int i = (unsigned int)key;
-        const long long p = key >> 32;
-        const float4 e = r.ev[i];
-        const int y = (int)p / W, x = (int)p - y * W; // (p < H * W <= 2^31 - 1)
-        const double t = (double)e.x;
+        const RowKey key = decode_key(r.sorted[j], W);
+        const unsigned int i = key.i;
+        const double t = (double)r.ev[i].x;
         double a[8];
         int m = 0;
 #pragma unroll
@@ -112,16 +104,11 @@ __global__ __launch_bounds__(256) void k_denoise_ages(AgesArgs r)
             for (int dx = -1; dx <= 1; ++dx) {
                 if (dx == 0 && dy == 0) continue;
                 double age = __longlong_as_double(0x7ff0000000000000LL); // +inf
-                const int qx = x + dx, qy = y + dy;
+                const int qx = key.x + dx, qy = key.y + dy;
                 if (qx >= 0 && qx < W && qy >= 0 && qy < H) {
-                    const long long q = p + (long long)dy * W + dx;
-                    const int lo = r.seg[q], hi = r.seg[q + 1];
-                    int s = lo, z = hi; // rows of q with an index below i: sorted[lo .. s)
-                    while (s < z) {
-                        const int mid = s + ((z - s) >> 1);
-                        if ((unsigned int)r.sorted[mid] < i) s = mid + 1; else z = mid;
-                    }
-                    const float tq = s > lo ? r.ev[(unsigned int)r.sorted[s - 1]].x : r.last_t[q];
+                    const long long q = key.p + (long long)dy * W + dx;
+                    unsigned int j_q;
+                    const float tq = latest_before(r.sorted, r.seg, q, i, &j_q) ? r.ev[j_q].x : r.last_t[q];
                     age = t - (double)tq; // (tq = -inf: +inf)
                 }
                 a[m++] = age;
@@ -139,22 +126,12 @@ __global__ __launch_bounds__(256) void k_denoise_ages(AgesArgs r)
         if (r.labels) {
             label = r.labels[i] ? 1 : 0;
         } else if (lb) {
-            const long long g = r.row0 + (long long)i;
-            int s = 0, z = r.n_lbounds; // entries <= g
-            while (s < z) {
-                const int mid = (s + z) >> 1;
-                if (lb[mid] <= g) s = mid + 1; else z = mid;
-            }
-            label = s & 1;
+            label = count_le<long long>(lb, r.n_lbounds, r.row0 + (long long)i) & 1;
         }
         int b = 0; // the bins ascend with k: each search starts at the bin before
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            int z = T;
-            while (b < z) {
-                const int mid = (b + z) >> 1;
-                if (s_taus[mid] < a[k]) b = mid + 1; else z = mid;
-            }
+            b = count_lt<double>(s_taus, T, a[k], b);
             atomicAdd(&s_hist[(k * 2 + label) * nb + b], 1);
         }
         if (r.keep) {
@@ -176,9 +153,7 @@ __global__ __launch_bounds__(256) void k_denoise_map_update(const float4 *__rest
                                                             const int *__restrict__ seg, long long npx, float *__restrict__ last_t)
 {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= npx) return;
-    const int lo = seg[p], hi = seg[p + 1];
-    if (hi > lo) last_t[p] = ev[(unsigned int)sorted[hi - 1]].x;
+    if (p < npx) map_update(ev, sorted, seg, p, last_t, nullptr);
 }
 
 } // namespace

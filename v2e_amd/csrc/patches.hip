@@ -15,8 +15,8 @@
 //                      the subtraction each rounded in float64; channel 1 = P_q where not none and age < tau, otherwise 0.
 //
 // The lookup "the latest earlier row at q" is denoise.hip's: v2e_denoise_keys gives row i the key pixel << 32 | i, the host sorts
-// the keys, v2e_denoise_segments finds each pixel's stretch, and a binary search of q's stretch finds the largest row index below i;
-// one 16-byte gather of that row supplies both t and p.  Every entry is then independent of every other, so the result depends on
+// the keys, v2e_denoise_segments finds each pixel's stretch, and rowkeys.h's latest_before searches q's stretch for that row;
+// one 16-byte gather of it supplies both t and p.  Every entry is then independent of every other, so the result depends on
 // the row order alone, not on scheduling or on how a clip is cut into calls or passes.
 //
 // Mapping: one thread per (row, offset), the rows taken in sorted-key (pixel) order as in k_denoise_ages: the P * P lanes of a row
@@ -53,31 +53,21 @@ __global__ __launch_bounds__(256) void k_patches_features(PatchArgs a)
 {
     constexpr int P = 2 * R + 1, PP = P * P;
     const int W = a.W, H = a.H;
-    const int n_seg = a.seg[(long long)H * W], n_valid = n_seg < a.n ? n_seg : a.n; // (no read past the pass's keys, whatever seg holds)
-    const long long total = (long long)n_valid * PP;
+    const long long total = (long long)valid_keys(a.seg, H, W, a.n) * PP;
     for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < total; g += (long long)gridDim.x * 256) {
         const int j = (int)(g / PP), o = (int)(g - (long long)j * PP);
-        const long long key = a.sorted[j];
-        const unsigned int i = (unsigned int)key;
-        const long long p = key >> 32;
-        if (i >= (unsigned int)a.n || p >= (long long)H * W) continue; // (not a key of this pass: nothing is written for it)
+        const RowKey key = decode_key(a.sorted[j], W);
+        const unsigned int i = key.i;
+        if (i >= (unsigned int)a.n || key.p >= (long long)H * W) continue; // (not a key of this pass: nothing is written for it)
         const float t = a.ev[i].x;
-        const int y = (int)p / W, x = (int)p - y * W; // (p < H * W <= 2^31 - 1)
         const int dy = o / P - R, dx = o - (o / P) * P - R;
-        const int qx = x + dx, qy = y + dy;
+        const int qx = key.x + dx, qy = key.y + dy;
         float f0 = a.mode ? 0.0f : pos_inf(), f1 = 0.0f; // none
         if (qx >= 0 && qx < W && qy >= 0 && qy < H) {
-            const long long q = p + (long long)dy * W + dx;
-            const int lo = a.seg[q], hi = a.seg[q + 1];
-            int s = lo, z = hi; // rows of q with an index below i: sorted[lo .. s)
-            unsigned int before = 0; // the row index of sorted[s - 1] once s > lo: the last probe that was below i
-            while (s < z) {
-                const int mid = s + ((z - s) >> 1);
-                const unsigned int v = (unsigned int)a.sorted[mid];
-                if (v < i) { s = mid + 1; before = v; } else z = mid;
-            }
+            const long long q = key.p + (long long)dy * W + dx;
+            unsigned int before;
             float tq, pq;
-            if (s > lo) {
+            if (latest_before(a.sorted, a.seg, q, i, &before)) {
                 const float4 e = a.ev[before];
                 tq = e.x;
                 pq = e.w > 0.0f ? 1.0f : -1.0f;
@@ -129,13 +119,7 @@ __global__ __launch_bounds__(256) void k_patches_map_update(const float4 *__rest
                                                             signed char *__restrict__ last_p)
 {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= npx) return;
-    const int lo = seg[p], hi = seg[p + 1];
-    if (hi > lo) {
-        const float4 e = ev[(unsigned int)sorted[hi - 1]];
-        last_t[p] = e.x;
-        last_p[p] = e.w > 0.0f ? 1 : -1;
-    }
+    if (p < npx) map_update(ev, sorted, seg, p, last_t, last_p);
 }
 
 } // namespace

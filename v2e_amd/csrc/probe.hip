@@ -10,6 +10,7 @@
 // All of them write float64 with plain stores into out[n_frames][P][V2E_PROBE_FIELDS] (field order: include/v2e_amd.h).  The
 // probed pixels travel by value in the launch (V2EProbeSet): nothing is uploaded, and a captured run bakes them in.
 #include "common.h"
+#include "table_search.h"
 
 namespace {
 
@@ -50,21 +51,10 @@ __global__ __launch_bounds__(V2E_PROBE_MAX) void k_probe_tap_emit(V2EProbeSet ps
     o[F_NEG] = scalar_thres ? neg_scalar : (double)neg[px];
 }
 
-// The frame of row i: the last record whose ev_offset is <= i (sinks.hip's search for v2e_events_pack_aedat2_run).
-__device__ __forceinline__ int frame_of_row(const v2e_frame_rec *__restrict__ recs, int nrec, long long i)
-{
-    int lo = 0, hi = nrec;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((long long)recs[mid].ev_offset <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // One pass over the run's rows (grid-stride; the number of rows is read from the last record, never more than cap).  A row's
 // pixel is looked up in the LDS table of probed pixels -- every lane reads the same entry, a broadcast -- and only a row that
-// hits one (a few in a million) searches for its frame and, if it is one of that frame's n_signal signal rows, adds one to the
-// integer counters cnt[frame][probe][OFF, ON] (zero on entry).  The workgroup that finishes last turns the counters into the two
+// hits one (a few in a million) searches for its frame (table_search.h: frame_of_row) and, if it is one of that frame's n_signal
+// signal rows, adds one to the integer counters cnt[frame][probe][OFF, ON] (zero on entry).  The workgroup that finishes last turns the counters into the two
 // float64 columns of out: integer atomics, so the result does not depend on the order of anything.
 __global__ __launch_bounds__(ROWS_BLOCK) void k_probe_count_rows(V2EProbeSet ps, const float4 *__restrict__ ev, unsigned long long cap,
                                                                  const v2e_frame_rec *__restrict__ recs, int n_frames, int W,

@@ -4,10 +4,11 @@
 // A recording holds records that are not rows (APS / IMU samples, special events, comment and malformed lines), so both decoders
 // are an ordered compaction over blocks of V2E_READER_BLOCK items: the kept items counted per block, an exclusive scan of the
 // block counts by one workgroup, and a write pass in which an item's place is its block's base plus the kept items before it in
-// the block (a ballot within its wave, the waves' counts through LDS).  The text decoder runs that twice: over the bytes for the
+// the block (block_ops.h: block_sum, block_bases, block_rank).  The text decoder runs that twice: over the bytes for the
 // line starts, then over the lines -- parsed one per lane from LDS where a block's lines fit -- for the rows.  Counters are
 // integer block sums added with integer atomics: every result is the same from run to run.
 #include "common.h"
+#include "block_ops.h"
 #include "text_parse.h"
 
 namespace {
@@ -26,54 +27,12 @@ __device__ __forceinline__ void add_counter(int64_t *c, long long v)
     if (v) atomicAdd((u64 *)c, (u64)v);
 }
 
-// sum of v over the workgroup, valid in thread 0 (s: one slot per wave)
-__device__ __forceinline__ int block_sum(int v, int *s)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads(); // s may still be read from an earlier sum
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int t = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += s[w];
-    return t;
-}
-
-// the number of kept items before this lane in its workgroup (s: one slot per wave)
-__device__ __forceinline__ int block_rank(bool keep, int *s)
-{
-    const u64 b = __ballot(keep);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) s[wave] = (int)__popcll(b);
-    __syncthreads();
-    int before = (int)__popcll(b & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) before += s[w];
-    return before;
-}
-
 // exclusive scan of blk[0 .. nblk) in place by one workgroup, the total to *total
 __global__ __launch_bounds__(1024) void k_rd_scan(long long *__restrict__ blk, int nblk, long long *__restrict__ total)
 {
     __shared__ long long s_part[1024];
-    const int tid = threadIdx.x;
-    const int per = (nblk + 1023) / 1024;
-    long long sum = 0;
-    for (int k = 0; k < per; ++k) { const int j = tid * per + k; if (j < nblk) sum += blk[j]; }
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const long long v = tid >= off ? s_part[tid - off] : 0;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    long long run = s_part[tid] - sum;
-    for (int k = 0; k < per; ++k) {
-        const int j = tid * per + k;
-        if (j < nblk) { const long long c = blk[j]; blk[j] = run; run += c; }
-    }
-    if (tid == 1023) *total = s_part[1023];
+    const long long t = block_bases(blk, nblk, s_part);
+    if (threadIdx.x == 1023) *total = t;
 }
 
 // ------------------------------------------------------------------------------------------------------------- AEDAT-2.0
@@ -213,13 +172,7 @@ __global__ __launch_bounds__(RB) void k_txt_line_starts(const char *__restrict__
     const uint32_t m = j * NL_BYTES < n_bytes ? newline_mask(bytes, n_bytes, j) : 0u;
     const int c = __popc(m);
     s_cnt[tid] = c;
-    __syncthreads();
-    for (int off = 1; off < RB; off <<= 1) { // inclusive scan of the lanes' counts
-        const int v = tid >= off ? s_cnt[tid - off] : 0;
-        __syncthreads();
-        s_cnt[tid] += v;
-        __syncthreads();
-    }
+    block_scan<RB>(s_cnt); // inclusive scan of the lanes' counts
     int64_t r = blk_base[blockIdx.x] + (s_cnt[tid] - c);
     if (j == 0) line_start[0] = 0;
     for (uint32_t mm = m; mm; mm &= mm - 1) {

@@ -6,8 +6,8 @@
 // packet ends in stays behind as `currentFrame`; the packet's last event is never accumulated (renderer.py:303-306).
 //
 // Here the windows are not walked: one launch (k_render_hist) puts every event into the frame(s) its window rule assigns
-// it to -- a binary search over the packet's window boundaries (DURATION: time stamps, an event exactly on a boundary
-// belongs to both neighbours, as searchsorted left / right give it; AREA_COUNT: the segment ends found by k_area_segments),
+// it to -- a binary search (table_search.h: count_le) over the packet's window boundaries (DURATION: time stamps, an event
+// exactly on a boundary belongs to both neighbours, as searchsorted left / right give it; AREA_COUNT: the segment ends found by k_area_segments),
 // an integer division (COUNT) -- and adds +-1 to that frame's bin; one launch (k_render_finish) clips and normalises all
 // frames of the packet.  k_area_segments is the one sequential rule (a cell counter that resets at every trigger): a
 // single wave walks the packet 64 events at a time, ranks the events of a chunk within their cells by ballot, and restarts
@@ -17,6 +17,7 @@
 // all packets by one single-wave kernel (DURATION: k_run_windows_duration, AREA_COUNT: k_run_area_segments), one histogram
 // launch in which every event first finds its packet, one finish launch, and the frame times on the device.
 #include "common.h"
+#include "table_search.h"
 
 namespace {
 
@@ -36,17 +37,6 @@ struct RenderArgs {
     int bins_y, bins_x;
     double y_lo, x_lo, delta_y, delta_x;
 };
-
-// number of entries of the sorted array a[0..n) that are <= v
-template <typename T> __device__ __forceinline__ int count_le(const T *__restrict__ a, int n, T v)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] <= v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(256) void k_render_hist(RenderArgs r)
 {

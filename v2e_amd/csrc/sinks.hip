@@ -5,23 +5,16 @@
 //   HDF5       v2ecore/emulator.py:955-965              (uint32 [N,4]: t_us, x, y, p with -1 -> 0)
 //   text       v2ecore/output/ae_text_output.py:86-101  (`t x y p[ label]\n`, t the repr of the float64; text_format.h)
 // Labels (label_signal_noise) follow the emulator's order of a frame's rows -- its n_signal signal events first, then the
-// noise -- per frame of a run: a row belongs to the last frame whose ev_offset is <= its index.
+// noise -- per frame of a run: a row belongs to the last frame whose ev_offset is <= its index (table_search.h: row_is_signal).
+// The passes that place their output by a count per block of rows (pack32's run table, the text lines) take their sums, ranks
+// and scans from block_ops.h.
 #include "common.h"
+#include "block_ops.h"
+#include "rowkeys.h"
+#include "table_search.h"
 #include "text_format.h"
 
 namespace {
-
-// 1: row i is a signal event, 0: noise.  recs == nullptr: one frame of n_signal0 signal rows at row 0 (the per-frame path)
-__host__ __device__ __forceinline__ int row_is_signal(int64_t i, const v2e_frame_rec *recs, int nrec, int64_t n_signal0)
-{
-    if (!recs) return i < n_signal0;
-    int lo = 0, hi = nrec;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((int64_t)recs[mid].ev_offset <= i) lo = mid; else hi = mid;
-    }
-    return i - (int64_t)recs[lo].ev_offset < (int64_t)recs[lo].n_signal;
-}
 
 __device__ __forceinline__ uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
 
@@ -118,27 +111,19 @@ __device__ __forceinline__ bool p32_starts_run(const float4 *__restrict__ ev, in
 __global__ __launch_bounds__(P32_BLOCK) void k_pack32_words(const float4 *__restrict__ ev, int64_t n, uint32_t *__restrict__ payload,
                                                             uint32_t *__restrict__ blk_runs, uint32_t *__restrict__ overflow)
 {
-    __shared__ uint32_t s_cnt[P32_BLOCK / 64];
+    __shared__ int s_cnt[P32_BLOCK / 64];
     const int64_t i = (int64_t)blockIdx.x * P32_BLOCK + threadIdx.x;
     bool start = false;
     if (i < n) {
         const float4 e = ev[i];
-        // fits: x an integer value in [0, 2048), y one in [0, 1024).  The float comparisons come first: they refuse NaN, negative
-        // and huge values, which the conversion to an integer does not define
-        const bool fits = e.y >= 0.0f && e.y < 2048.0f && e.z >= 0.0f && e.z < 1024.0f && truncf(e.y) == e.y && truncf(e.z) == e.z;
-        const uint32_t x = fits ? (uint32_t)e.y : 0u, y = fits ? (uint32_t)e.z : 0u;
+        const int x = pixel_coord(e.y, 2048), y = pixel_coord(e.z, 1024);
+        const bool fits = x >= 0 && y >= 0;
         if (!fits) atomicOr(overflow, 1u); // does not fit 11 + 10 bits: the caller falls back to pack64
-        payload[i] = x | (y << 11) | (e.w > 0.f ? 1u << 21 : 0u);
+        payload[i] = (fits ? (uint32_t)x | ((uint32_t)y << 11) : 0u) | (e.w > 0.f ? 1u << 21 : 0u);
         start = p32_starts_run(ev, i);
     }
-    const unsigned long long b = __ballot(start);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < P32_BLOCK / 64; ++w) t += s_cnt[w];
-        blk_runs[blockIdx.x] = t;
-    }
+    const int t = block_count(start, s_cnt, P32_BLOCK / 64);
+    if (threadIdx.x == 0) blk_runs[blockIdx.x] = (uint32_t)t;
 }
 
 // pass 2: exclusive scan of the per-block run counts (one workgroup; nblk <= 2^22), total to runs[0]
@@ -146,28 +131,11 @@ __global__ __launch_bounds__(1024) void k_pack32_scan(uint32_t *__restrict__ blk
                                                       int64_t cap_runs, uint32_t *__restrict__ overflow)
 {
     __shared__ uint32_t s_part[1024];
-    const int tid = threadIdx.x;
-    const int per = (nblk + 1023) / 1024;
-    uint32_t sum = 0;
-    for (int k = 0; k < per; ++k) { const int j = tid * per + k; if (j < nblk) sum += blk_runs[j]; }
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) { // Hillis-Steele inclusive scan
-        const uint32_t v = tid >= off ? s_part[tid - off] : 0u;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = s_part[tid] - sum;
-    for (int k = 0; k < per; ++k) {
-        const int j = tid * per + k;
-        if (j < nblk) { const uint32_t c = blk_runs[j]; blk_runs[j] = run; run += c; }
-    }
-    if (tid == 1023) {
+    const uint32_t total = block_bases(blk_runs, nblk, s_part);
+    if (threadIdx.x == 1023) {
         // runs[0]: the number of blocks IN THE TABLE (never more than it holds: a receiver searches runs[1 .. 1 + R)), and in
         // bits 62 / 63 what went wrong -- a coordinate that does not fit, a table that was too small -- so that every rank
         // that receives the table sees it, not only the sender
-        const uint32_t total = s_part[1023];
         uint32_t fl = *overflow & 1u; // k_pack32_words ran before this kernel on the same stream
         if ((int64_t)total > cap_runs) { fl |= 2u; atomicOr(overflow, 2u); }
         const unsigned long long kept = (int64_t)total > cap_runs ? (unsigned long long)cap_runs : (unsigned long long)total;
@@ -179,17 +147,12 @@ __global__ __launch_bounds__(1024) void k_pack32_scan(uint32_t *__restrict__ blk
 __global__ __launch_bounds__(P32_BLOCK) void k_pack32_runs(const float4 *__restrict__ ev, int64_t n, const uint32_t *__restrict__ blk_base,
                                                            unsigned long long *__restrict__ runs, int64_t cap_runs)
 {
-    __shared__ uint32_t s_cnt[P32_BLOCK / 64];
+    __shared__ int s_cnt[P32_BLOCK / 64];
     const int64_t i = (int64_t)blockIdx.x * P32_BLOCK + threadIdx.x;
     const bool start = i < n && p32_starts_run(ev, i);
-    const unsigned long long b = __ballot(start);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) s_cnt[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
-    uint32_t before = blk_base[blockIdx.x];
-    for (int w = 0; w < wave; ++w) before += s_cnt[w];
+    const int before = block_rank(start, s_cnt);
     if (start) {
-        const uint32_t r = before + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+        const uint32_t r = blk_base[blockIdx.x] + (uint32_t)before;
         if ((int64_t)r < cap_runs) runs[1 + r] = ((unsigned long long)__float_as_uint(ev[i].x) << 32) | (unsigned long long)(uint32_t)i;
     }
 }
@@ -201,7 +164,9 @@ __global__ __launch_bounds__(256) void k_unpack32(const uint32_t *__restrict__ p
     if (i >= n) return;
     const int nr = (int)(runs[0] & 0xFFFFFFFFull); // bits 62 / 63: the sender's overflow flags (the host refuses such a table)
     if (nr <= 0) return;
-    int lo = 0, hi = nr; // last run whose first event index is <= i
+    // The last run whose first event index (the low word of its entry) is <= i.  Its own loop, not table_search.h's first_not:
+    // through that this kernel measured 2 % slower (profiles/r21_event_rows_refactor.txt)
+    int lo = 0, hi = nr;
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
         if ((int64_t)(uint32_t)runs[1 + mid] <= i) lo = mid; else hi = mid;
@@ -232,38 +197,16 @@ __global__ __launch_bounds__(TXT_BLOCK) void k_text_len(const float4 *__restrict
         const float4 e = ev[i];
         len = v2e_tf::put_line<false>(nullptr, e.x, e.y, e.z, e.w, text_label(i, labels, recs, nrec, n_signal0));
     }
-    for (int o = 32; o > 0; o >>= 1) len += __shfl_down(len, o, 64);
-    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = len;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long t = 0;
-        for (int w = 0; w < TXT_BLOCK / 64; ++w) t += s_sum[w];
-        blk[blockIdx.x] = t;
-    }
+    const int t = block_sum(len, s_sum);
+    if (threadIdx.x == 0) blk[blockIdx.x] = t;
 }
 
 // exclusive scan of the per-block byte counts in place (one workgroup), the total to *total
 __global__ __launch_bounds__(1024) void k_text_scan(long long *__restrict__ blk, int nblk, long long *__restrict__ total)
 {
     __shared__ long long s_part[1024];
-    const int tid = threadIdx.x;
-    const int per = (nblk + 1023) / 1024;
-    long long sum = 0;
-    for (int k = 0; k < per; ++k) { const int j = tid * per + k; if (j < nblk) sum += blk[j]; }
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const long long v = tid >= off ? s_part[tid - off] : 0;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    long long run = s_part[tid] - sum;
-    for (int k = 0; k < per; ++k) {
-        const int j = tid * per + k;
-        if (j < nblk) { const long long c = blk[j]; blk[j] = run; run += c; }
-    }
-    if (tid == 1023) *total = s_part[1023];
+    const long long t = block_bases(blk, nblk, s_part);
+    if (threadIdx.x == 1023) *total = t;
 }
 
 __global__ __launch_bounds__(TXT_BLOCK) void k_text_write(const float4 *__restrict__ ev, int64_t n, int labels,
@@ -284,13 +227,7 @@ __global__ __launch_bounds__(TXT_BLOCK) void k_text_write(const float4 *__restri
         len = v2e_tf::put_line<false>(nullptr, e.x, e.y, e.z, e.w, lab);
     }
     s_off[tid] = len;
-    __syncthreads();
-    for (int off = 1; off < TXT_BLOCK; off <<= 1) { // inclusive scan of the line lengths
-        const int v = tid >= off ? s_off[tid - off] : 0;
-        __syncthreads();
-        s_off[tid] += v;
-        __syncthreads();
-    }
+    block_scan<TXT_BLOCK>(s_off); // inclusive: a line ends at s_off[tid]
     if (i < n) v2e_tf::put_line<true>(s_text + (s_off[tid] - len), e.x, e.y, e.z, e.w, lab);
     __syncthreads();
     const int nbytes = s_off[TXT_BLOCK - 1];

@@ -6,14 +6,17 @@
 // tensorizer, every other window's plane lies in the launch's output.  Window k = [B_k, B_k+1), float64 throughout:
 //   uniform   B_k = t_start + (double)k * window_s (one product, one sum; the library is built with -ffp-contract=off), k from
 //             floor((t - t_start) / window_s), corrected by +-1 against B_k and B_k+1
-//   explicit  an ascending float64 table, binary search (staged in LDS when it fits)
-// so that k == searchsorted(B, t, 'right') - 1 in both.
+//   explicit  an ascending float64 table, table_search.h's count_le (staged in LDS when it fits)
+// so that k == searchsorted(B, t, 'right') - 1 in both.  A row takes part if x / y is a coordinate of the sensor (rowkeys.h:
+// pixel_coord), p is +-1 and t is not NaN.
 //
 // All scattered updates are no-return INTEGER atomics, so the result does not depend on the order the rows arrive in: count adds 1
 // to an int32, voxel adds +-q (the bilinear weight in units of 2^-24) to an int64, the time surface takes the maximum of an
 // order-preserving uint32 key of the float32 time stamp.  The finish kernels turn the voxel sums into float32 and the keys,
 // by a running maximum over the windows, into time stamps.  Everything is enqueued on the caller's stream.
 #include "common.h"
+#include "block_ops.h"
+#include "rowkeys.h"
 
 namespace {
 
@@ -51,12 +54,6 @@ struct ScatterArgs {
     unsigned long long *counters; // n_bad, n_before, n_after; or null
 };
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_tensorize_scatter(ScatterArgs r)
 {
     extern __shared__ double s_bounds[];
@@ -72,10 +69,8 @@ __global__ __launch_bounds__(256) void k_tensorize_scatter(ScatterArgs r)
     unsigned long long n_bad = 0, n_before = 0, n_after = 0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < r.n; i += (long long)gridDim.x * 256) {
         const float4 e = r.ev[i];
-        const int x = (int)e.y, y = (int)e.z;
-        // (the float comparisons come first: they refuse NaN and everything the int conversion cannot hold)
-        if (!(e.y >= 0.0f && e.y < (float)r.W && e.z >= 0.0f && e.z < (float)r.H && (float)x == e.y && (float)y == e.z &&
-              (e.w == 1.0f || e.w == -1.0f) && e.x == e.x)) { ++n_bad; continue; }
+        const int x = pixel_coord(e.y, r.W), y = pixel_coord(e.z, r.H);
+        if (x < 0 || y < 0 || !(e.w == 1.0f || e.w == -1.0f) || e.x != e.x) { ++n_bad; continue; }
         const double t = (double)e.x;
         if (t < lo) { ++n_before; continue; }
         if (!(t < hi)) { ++n_after; continue; }
@@ -89,12 +84,7 @@ __global__ __launch_bounds__(256) void k_tensorize_scatter(ScatterArgs r)
             else if (t >= bk1) { ++kk; bk = bk1; bk1 = r.t_start + (double)(kk + 1) * r.window_s; }
             k = (int)(kk - r.k0);
         } else {
-            int a = 0, z = r.nk + 1; // entries <= t; at least one (t >= lo), at most nk (t < hi)
-            while (a < z) {
-                const int mid = (a + z) >> 1;
-                if (b[mid] <= t) a = mid + 1; else z = mid;
-            }
-            k = a - 1;
+            k = count_le<double>(b, r.nk + 1, t) - 1; // entries <= t: at least one (t >= lo), at most nk (t < hi)
             bk = b[k];
             bk1 = b[k + 1];
         }

@@ -30,12 +30,12 @@ import math
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, _rowpasses
 from ._capi import check, ptr, stream_ptr
+from ._rowpasses import DEFAULT_ROWS_PER_PASS
 
 MAX_TAUS = 256
 NEIGHBOURS = 8
-DEFAULT_ROWS_PER_PASS = 1 << 25
 
 
 def _check_taus(taus):
@@ -132,13 +132,9 @@ class DenoiseSweep(object):
     (module docstring)."""
 
     def __init__(self, height, width, taus, max_rows_per_pass=DEFAULT_ROWS_PER_PASS, device="cuda:0"):
-        self.height, self.width = int(height), int(width)
-        if self.height < 1 or self.width < 1 or self.height * self.width > 0x7FFFFFFF:
-            raise ValueError("DenoiseSweep: height and width must be positive (and height * width below 2^31)")
+        self.height, self.width = _rowpasses.check_sensor("DenoiseSweep", height, width)
         self.taus = _check_taus(taus)
-        self.max_rows_per_pass = int(max_rows_per_pass)
-        if not 1 <= self.max_rows_per_pass <= 1 << 30:
-            raise ValueError("DenoiseSweep: max_rows_per_pass must be in 1 .. 2^30")
+        self.max_rows_per_pass = _rowpasses.check_rows_per_pass("DenoiseSweep", max_rows_per_pass)
         self.device = torch.device(device)
         self.passes = 0        # row blocks processed so far
         self._state = None     # the device buffers, allocated by the first call that needs them
@@ -146,15 +142,14 @@ class DenoiseSweep(object):
     # ------------------------------------------------------------------------------------------------------------ device state
     def _dev(self):
         if self._state is None:
-            if not torch.cuda.is_available():
-                raise _capi.V2EAmdError("v2e_amd.DenoiseSweep needs a ROCm GPU; there is no CPU fallback")
+            _capi.require_gpu("DenoiseSweep")
             dev, H, W, T = self.device, self.height, self.width, len(self.taus)
             self._state = {
                 "last_t": torch.full((H, W), -math.inf, dtype=torch.float32, device=dev),
                 "hist": torch.zeros((NEIGHBOURS, 2, T + 1), dtype=torch.int64, device=dev),
                 "n_bad": torch.zeros((), dtype=torch.int64, device=dev),
                 "taus": torch.from_numpy(self.taus).to(dev),
-                "seg": torch.empty((H * W + 1,), dtype=torch.int32, device=dev),
+                "seg": _rowpasses.new_seg(H, W, dev),
             }
         return self._state
 
@@ -212,8 +207,8 @@ class DenoiseSweep(object):
         st = self._dev()
         dev = self.device
         if n == 0:
-            zero = torch.zeros((), dtype=torch.int64, device=dev)
-            return {"n": zero, "n_bad": zero.clone(), "mask": None if keep is None else torch.zeros((0,), dtype=torch.bool, device=dev)}
+            zero, zero_bad = _rowpasses.no_rows(dev)
+            return {"n": zero, "n_bad": zero_bad, "mask": None if keep is None else torch.zeros((0,), dtype=torch.bool, device=dev)}
         rows = rows.to(dev).contiguous()
         lib = _capi.lib()
         stream = stream_ptr(dev)
@@ -221,26 +216,17 @@ class DenoiseSweep(object):
         lab = None if labels is None else labels.to(dev, non_blocking=True).to(torch.uint8).contiguous()
         lb = None if bounds is None else self._upload(bounds)
         mask = None if keep is None else torch.empty((n,), dtype=torch.uint8, device=dev)
-        cnt = torch.zeros((2,), dtype=torch.int64, device=dev)
         k, tau = keep if keep is not None else (1, 0.0)
-        for r0 in range(0, n, self.max_rows_per_pass):
-            m = min(self.max_rows_per_pass, n - r0)
-            ev = rows[r0:r0 + m]
-            keep_p = None if mask is None else C.c_void_p(mask.data_ptr() + r0)
-            keys = torch.empty((m,), dtype=torch.int64, device=dev)
-            check(lib.v2e_denoise_keys(ptr(ev), m, H, W, ptr(keys), keep_p, stream), "v2e_denoise_keys")
-            skeys = torch.sort(keys)[0]
-            del keys
-            check(lib.v2e_denoise_segments(ptr(skeys), m, H, W, ptr(st["seg"]), ptr(cnt), stream), "v2e_denoise_segments")
+        run = _rowpasses.RowPasses(self, rows, st["seg"], keep=mask)
+        for r0, m, ev, skeys in run:
             check(lib.v2e_denoise_ages(ptr(ev), m, H, W, ptr(skeys), ptr(st["seg"]), ptr(st["last_t"]), ptr(st["taus"]), T,
                                        None if lab is None else C.c_void_p(lab.data_ptr() + r0), ptr(lb),
-                                       0 if lb is None else int(lb.shape[0]), r0, ptr(st["hist"]), keep_p, k, tau, stream),
+                                       0 if lb is None else int(lb.shape[0]), r0, ptr(st["hist"]), run.keep_ptr(r0), k, tau, stream),
                   "v2e_denoise_ages")
             check(lib.v2e_denoise_map_update(ptr(ev), ptr(skeys), ptr(st["seg"]), H, W, ptr(st["last_t"]), stream),
                   "v2e_denoise_map_update")
-            self.passes += 1
-        st["n_bad"] += cnt[1]
-        return {"n": cnt[0], "n_bad": cnt[1], "mask": None if mask is None else mask.view(torch.bool)}
+        st["n_bad"] += run.n_bad
+        return {"n": run.n, "n_bad": run.n_bad, "mask": None if mask is None else mask.view(torch.bool)}
 
     def result(self):
         """The histogram so far as a DenoiseResult: one small read-back (it waits for the runs enqueued so far)."""

@@ -36,9 +36,10 @@ import math
 
 import torch
 
-from . import _capi
+from . import _capi, _rowpasses
 from ._capi import check, ptr, stream_ptr
-from .denoise import DEFAULT_ROWS_PER_PASS, label_bounds
+from ._rowpasses import DEFAULT_ROWS_PER_PASS
+from .denoise import label_bounds
 
 MODES = {"age": 0, "linear": 1}
 MAX_RADIUS = 3
@@ -49,9 +50,7 @@ class EventPatches(object):
 
     def __init__(self, height, width, radius=3, mode="linear", tau=0.1, device="cuda", max_rows_per_pass=DEFAULT_ROWS_PER_PASS,
                  max_output_bytes=8 << 30):
-        self.height, self.width = int(height), int(width)
-        if self.height < 1 or self.width < 1 or self.height * self.width > 0x7FFFFFFF:
-            raise ValueError("EventPatches: height and width must be positive (and height * width below 2^31)")
+        self.height, self.width = _rowpasses.check_sensor("EventPatches", height, width)
         if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= MAX_RADIUS:
             raise ValueError("EventPatches: radius must be 1, 2 or %d, got %r" % (MAX_RADIUS, radius))
         self.radius = int(radius)
@@ -65,9 +64,7 @@ class EventPatches(object):
             raise ValueError("EventPatches: tau must be a number, got %r" % (tau,)) from None
         if mode == "linear" and not (math.isfinite(self.tau) and self.tau > 0):
             raise ValueError("EventPatches: mode 'linear' needs a finite tau > 0, got %r" % (tau,))
-        self.max_rows_per_pass = int(max_rows_per_pass)
-        if not 1 <= self.max_rows_per_pass <= 1 << 30:
-            raise ValueError("EventPatches: max_rows_per_pass must be in 1 .. 2^30")
+        self.max_rows_per_pass = _rowpasses.check_rows_per_pass("EventPatches", max_rows_per_pass)
         self.max_output_bytes = int(max_output_bytes)
         if self.max_output_bytes < 0:
             raise ValueError("EventPatches: max_output_bytes must be >= 0")
@@ -78,13 +75,12 @@ class EventPatches(object):
     # ------------------------------------------------------------------------------------------------------------ device state
     def _dev(self):
         if self._state is None:
-            if not torch.cuda.is_available():
-                raise _capi.V2EAmdError("v2e_amd.EventPatches needs a ROCm GPU; there is no CPU fallback")
+            _capi.require_gpu("EventPatches")
             dev, H, W = self.device, self.height, self.width
             self._state = {
                 "last_t": torch.full((H, W), -math.inf, dtype=torch.float32, device=dev),
                 "last_p": torch.zeros((H, W), dtype=torch.int8, device=dev),
-                "seg": torch.empty((H * W + 1,), dtype=torch.int32, device=dev),
+                "seg": _rowpasses.new_seg(H, W, dev),
             }
         return self._state
 
@@ -130,31 +126,23 @@ class EventPatches(object):
         st = self._dev()
         dev = self.device
         if n == 0:
-            zero = torch.zeros((), dtype=torch.int64, device=dev)
+            zero, zero_bad = _rowpasses.no_rows(dev)
             feats = out[:0] if out is not None else torch.empty((0, 2, P, P), dtype=torch.float32, device=dev)
-            return {"features": feats, "valid": torch.zeros((0,), dtype=torch.bool, device=dev), "n": zero, "n_bad": zero.clone()}
+            return {"features": feats, "valid": torch.zeros((0,), dtype=torch.bool, device=dev), "n": zero, "n_bad": zero_bad}
         rows = rows.to(dev).contiguous()
         lib = _capi.lib()
         stream = stream_ptr(dev)
         H, W = self.height, self.width
         feats = out[:n] if out is not None else torch.empty((n, 2, P, P), dtype=torch.float32, device=dev)
         valid = torch.empty((n,), dtype=torch.uint8, device=dev)
-        cnt = torch.zeros((2,), dtype=torch.int64, device=dev)
-        for r0 in range(0, n, self.max_rows_per_pass):
-            m = min(self.max_rows_per_pass, n - r0)
-            ev = rows[r0:r0 + m]
-            keys = torch.empty((m,), dtype=torch.int64, device=dev)
-            check(lib.v2e_denoise_keys(ptr(ev), m, H, W, ptr(keys), None, stream), "v2e_denoise_keys")
-            skeys = torch.sort(keys)[0]
-            del keys
-            check(lib.v2e_denoise_segments(ptr(skeys), m, H, W, ptr(st["seg"]), ptr(cnt), stream), "v2e_denoise_segments")
+        run = _rowpasses.RowPasses(self, rows, st["seg"])
+        for r0, m, ev, skeys in run:
             check(lib.v2e_patches_features(ptr(ev), m, H, W, ptr(skeys), ptr(st["seg"]), ptr(st["last_t"]), ptr(st["last_p"]),
                                            self.radius, MODES[self.mode], self.tau, ptr(feats[r0:r0 + m]), ptr(valid[r0:r0 + m]), stream),
                   "v2e_patches_features")
             check(lib.v2e_patches_map_update(ptr(ev), ptr(skeys), ptr(st["seg"]), H, W, ptr(st["last_t"]), ptr(st["last_p"]), stream),
                   "v2e_patches_map_update")
-            self.passes += 1
-        return {"features": feats, "valid": valid.view(torch.bool), "n": cnt[0], "n_bad": cnt[1]}
+        return {"features": feats, "valid": valid.view(torch.bool), "n": run.n, "n_bad": run.n_bad}
 
 
 def frame_labels(counts, n_signal, device=None):

@@ -132,8 +132,7 @@ class EventRenderer(object):
         self.currentFrameStartTime = None
         self.currentFrame = None  # device float64 [h,w] while a frame is being filled, else None
         self.printed_empty_packet_warning = False
-        if not torch.cuda.is_available():
-            raise _capi.V2EAmdError("v2e_amd.EventRenderer needs a ROCm GPU; there is no CPU fallback")
+        _capi.require_gpu("EventRenderer")
         self.device = torch.device(device)
         self._acc = None
         # whole runs (render_run): rows appended and not yet flushed, the DURATION start time on the device, read-backs made

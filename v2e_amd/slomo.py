@@ -252,8 +252,7 @@ class SuperSloMo(object):
         order (a batch_size too large for two batches is halved, with a warning, as the reference does)."""
         if not output_folder:
             raise ValueError('output_folder is None; it must be supplied to store the interpolated frames')
-        if self.device == "cpu":
-            raise _capi.V2EAmdError("v2e_amd.SuperSloMo needs a ROCm GPU; there is no CPU fallback")
+        _capi.require_gpu("SuperSloMo", self.device != "cpu")
         nframes = len(os.listdir(source_frame_path))
         if nframes / self.batch_size < 2:
             logger.warning(f'only {nframes} input frames with batch_size={self.batch_size}, automatically '

@@ -48,8 +48,7 @@ class SloMoEngine:
         if conv_math is None:
             conv_math = os.environ.get("V2E_AMD_CONV_MATH", "auto")
         self.conv_math = conv_math
-        if not torch.cuda.is_available():
-            raise _capi.V2EAmdError("v2e_amd.SloMoEngine needs a ROCm GPU; there is no CPU fallback")
+        _capi.require_gpu("SloMoEngine")
         self.device = torch.device(device)
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())

@@ -196,8 +196,7 @@ class ThresholdSweep(object):
         """frames: uint8 [F,H,W] on the device; t_frames[F].  Enqueued on the current stream behind whatever produced the frames;
         returns a SweepResult (the counts are read back, so the call waits for them)."""
         t = self._check_frames(frames, t_frames)
-        if not torch.cuda.is_available():
-            raise _capi.V2EAmdError("v2e_amd.ThresholdSweep needs a ROCm GPU; there is no CPU fallback")
+        _capi.require_gpu("ThresholdSweep")
         lib = _capi.lib()
         dev = frames.device
         frames = frames.contiguous()
@@ -285,8 +284,7 @@ class ThresholdSweep(object):
         of the clip (module docstring); those runs wait for their events."""
         t = self._check_frames(frames, t_frames, "add_run", 1)
         frame0 = check_continuation(self.frames_seen, self._t_last, t, frame0)
-        if not torch.cuda.is_available():
-            raise _capi.V2EAmdError("v2e_amd.ThresholdSweep needs a ROCm GPU; there is no CPU fallback")
+        _capi.require_gpu("ThresholdSweep")
         lib = _capi.lib()
         dev = frames.device
         frames = frames.contiguous()

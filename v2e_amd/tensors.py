@@ -115,8 +115,7 @@ class EventTensorizer(object):
         if self.max_scratch_bytes < 1:
             raise ValueError("EventTensorizer: max_scratch_bytes must be positive")
         self.frame_times = None if frame_times is None else np.asarray(frame_times, dtype=np.float64).reshape(-1)
-        if not torch.cuda.is_available():
-            raise _capi.V2EAmdError("v2e_amd.EventTensorizer needs a ROCm GPU; there is no CPU fallback")
+        _capi.require_gpu("EventTensorizer")
         self.device = dev = torch.device(device)
         H, W, B = self.height, self.width, self.voxel_bins
         self.k_open = 0          # clip index of the open window: the first one not handed out yet
