@@ -818,6 +818,36 @@ int v2e_patches_features(const float *events, int64_t n, int H, int W, const int
 int v2e_patches_map_update(const float *events, const int64_t *sorted_keys, const int32_t *seg, int H, int W, float *last_t, int8_t *last_p,
                            void *stream);
 
+/* A stream's own statistics: per-pixel counts, same-pixel inter-event intervals and time-bin counts of the rows of device-resident
+ * runs (v2e_amd/csrc/stats.hip; host side v2e_amd/stats.py, EventStats).
+ * Rows and validity: rows are events[n][4] = (t, x = column, y = row, p), taken in row order; a row is bad under exactly
+ * DenoiseSweep's rule, is counted by v2e_denoise_segments and touches nothing.  A valid row is ON iff p > 0; its label is
+ * v2e_denoise_ages' (labels, or label_bounds with row0, or neither: signal).  With c = 2 * label + ON:
+ * count (uint64 [4][H][W]): count[c][y][x] += 1 for every valid row.  Everything else takes the valid rows inside the ROI
+ * x0 <= x <= x1, y0 <= y <= y1 only:
+ * the previous event of row i is the latest valid row j < i at its pixel in this pass, else the carried last_t (float32 [H][W],
+ * starts at -inf: none) / last_p (int8 [H][W], +-1, starts at 0).  None: sums[c] += 1 (n_first).  Otherwise
+ * d = (double)t_i - (double)T_prev, tr = 2 * (previous ON) + ON, isi_hist[label][tr][the number of isi_edges <= d] += 1 (uint64
+ * [2][4][n_edges+1]; 1 to 256 edges, ascending: the caller checks); d < 0: sums[4 + label] += 1 (n_backwards); d >= 0:
+ * sums[8 + 4 * label + tr] = the unsigned minimum of itself and d's bit pattern (min_isi; the caller starts it at +inf's bits).
+ * time_bounds (n_bins + 1 ascending doubles, 1 <= n_bins <= 2^20; or null with n_bins 0): k = (the number of bounds <= (double)t)
+ * - 1; time_hist[c][k] += 1 (uint64 [4][n_bins]) for 0 <= k < n_bins, else sums[6] += 1 (before) or sums[7] += 1 (after).
+ * sums[16] / sums[17]: the minimum / maximum over ALL valid rows of key(t), key(v) = bits ^ 0xffffffff for a negative float32,
+ * bits | 0x80000000 otherwise (the caller starts them at 0xffffffff / 0).  sums is uint64 [18].
+ * isi_hist and time_hist are given as isi_replicas / time_replicas (1 to 2048) copies of those shapes, all zero at the start; workgroup
+ * b of the kernel adds to copy b % replicas and the histogram is the sum of the copies (one copy of a small table is one contended
+ * atomic per row).
+ * Integer atomics only: the result depends on the row order alone.
+ * One pass (n <= 2^31 - 1 rows, H * W <= 2^31 - 1) is v2e_denoise_keys, a sort of the keys, v2e_denoise_segments, then:
+ * v2e_stats_rows: all sums; the maps are only read.  events must be 16-byte aligned.
+ * v2e_stats_map_update: last_t[p], last_p[p] from pixel p's last row of the pass; behind v2e_stats_rows on the same stream. */
+int v2e_stats_rows(const float *events, int64_t n, int H, int W, const int64_t *sorted_keys, const int32_t *seg, const float *last_t,
+                   const int8_t *last_p, int x0, int x1, int y0, int y1, const double *isi_edges, int n_edges, const double *time_bounds,
+                   int n_bins, const uint8_t *labels, const int64_t *label_bounds, int n_label_bounds, int64_t row0, uint64_t *count,
+                   uint64_t *isi_hist, int isi_replicas, uint64_t *time_hist, int time_replicas, uint64_t *sums, void *stream);
+int v2e_stats_map_update(const float *events, const int64_t *sorted_keys, const int32_t *seg, int H, int W, float *last_t, int8_t *last_p,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,9 @@ SIGNATURES = {
     "v2e_denoise_map_update": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "v2e_patches_features": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp]),
     "v2e_patches_map_update": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "v2e_stats_rows": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _i, _vp,
+                            _i, _vp, _vp]),
+    "v2e_stats_map_update": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
 }
 
 # dev entry points the library exports outside include/v2e_amd.h: typed by lib() when present, never required
