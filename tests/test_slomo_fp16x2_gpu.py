@@ -8,88 +8,14 @@ several of them (its 32-channel layers sit at full resolution, h % 32 == 0 and w
 Range slots: what v2e_unet_forward leaves in its 32 slot words (the float32 bits of the largest |value| of the input and of every
 convolution's output), bit for bit against the tensors of the same pass, and the power of two a two-piece layer derives from them.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
-from test_slomo_gpu import TOL, _rand, relerr
+from slomo_layers import _Layer, _case_tensors
+from test_slomo_gpu import TOL, relerr
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 1 << 14           # floats of guard band on either side of every tensor a layer reads or writes
-BAND_BITS = 0x7FC0BEEF    # what the output's bands hold (a NaN with a payload: any write shows, and so does a copy of it)
-
-
-class _Layer:
-    """One convolution's weights packed for the three kernel families, run through v2e_conv2d_lrelu on tensors that live inside
-    larger device buffers: NaN around the inputs, sentinel bands around the output (checked after every launch)."""
-
-    def __init__(self, wt, b):
-        from v2e_amd import _capi
-        from v2e_amd.slomo import weight_scale_log2
-        self.lib, self.check = _capi.lib(), _capi.check
-        self.dev = torch.device("cuda")
-        self.co, self.ci, self.k, _ = wt.shape
-        co, ci, k = self.co, self.ci, self.k
-        s = self._stream()
-        tw = torch.from_numpy(wt).to(self.dev)
-        self.tb = torch.from_numpy(b).to(self.dev)
-        self.wp = torch.empty((ci, k, k, co), dtype=torch.float32, device=self.dev)
-        self.check(self.lib.v2e_pack_conv_weight(C.c_void_p(tw.data_ptr()), C.c_void_p(self.wp.data_ptr()), co, ci, k, s), "pack")
-        cpad = (ci + 15) // 16 * 16
-        self.w3 = torch.empty(cpad * k * k * co * 6, dtype=torch.uint8, device=self.dev)
-        self.check(self.lib.v2e_pack_conv_weight_s3(C.c_void_p(tw.data_ptr()), C.c_void_p(self.w3.data_ptr()), co, ci, k, s), "pack_s3")
-        # the product's rule for the weights' power of two (HipUNet calls the same function on the same number)
-        self.sl2 = weight_scale_log2(float(tw.abs().max()))
-        self.w2 = torch.empty(cpad * k * k * co * 4, dtype=torch.uint8, device=self.dev)
-        self.check(self.lib.v2e_pack_conv_weight_h2(C.c_void_p(tw.data_ptr()), C.c_void_p(self.w2.data_ptr()), co, ci, k, self.sl2, s),
-                   "pack_h2")
-        torch.cuda.synchronize()
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    def _desc(self, math):
-        from v2e_amd._capi import ConvDesc
-        d = ConvDesc(self.wp.data_ptr(), self.tb.data_ptr(), self.ci, self.co, self.k)
-        if math == "bf16x3":
-            d.weight_s3, d.split_kind = self.w3.data_ptr(), 0
-        elif math == "fp16x2":
-            d.weight_s3, d.split_kind = self.w2.data_ptr(), 2 | (self.sl2 << 8)
-        else:
-            assert math == "f32"
-        return d
-
-    def _banded_input(self, x):
-        buf = torch.full((GUARD + x.size + GUARD,), float("nan"), dtype=torch.float32, device=self.dev)
-        view = buf[GUARD:GUARD + x.size].view(x.shape)
-        view.copy_(torch.from_numpy(x))
-        return buf, view
-
-    def run(self, x0, x1, math):
-        n, _, h, w = x0.shape
-        b0, t0 = self._banded_input(x0)
-        b1, t1 = self._banded_input(x1) if x1 is not None else (None, None)
-        ny = n * self.co * h * w
-        ybuf = torch.full((GUARD + ny + GUARD,), BAND_BITS, dtype=torch.int32, device=self.dev).view(torch.float32)
-        y = ybuf[GUARD:GUARD + ny].view(n, self.co, h, w)
-        y.fill_(float("nan"))
-        d = self._desc(math)
-        self.check(self.lib.v2e_conv2d_lrelu(C.c_void_p(t0.data_ptr()), x0.shape[1], C.c_void_p(t1.data_ptr()) if t1 is not None else None,
-                                             0 if x1 is None else x1.shape[1], 0, C.byref(d), C.c_void_p(y.data_ptr()), n, h, w,
-                                             self._stream()), "conv")
-        torch.cuda.synchronize()
-        bits = ybuf.view(torch.int32)
-        assert bool((bits[:GUARD] == BAND_BITS).all()), "%s wrote in front of its output" % math
-        assert bool((bits[GUARD + ny:] == BAND_BITS).all()), "%s wrote behind its output" % math
-        for buf, x in ((b0, x0), (b1, x1)):   # and the inputs and their surroundings are as they were
-            if buf is not None:
-                assert bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[GUARD + x.size:]).all())
-                assert np.array_equal(buf[GUARD:GUARD + x.size].cpu().numpy(), x.ravel())
-        return y.cpu().numpy()
-
 
 # (k, cin0, cin1, cout, n, h, w): every `return launch_conv_s3<KS, CT, PT, WP, TW, NB, MODE, RG, 2>` of conv_dispatch_h2, the two-piece
 # tile selection.  A tile is WP * PT * 32 / TW rows of TW pixels; "ragged" = the last tile row partly masked.
@@ -150,17 +76,6 @@ H2_FALLBACK_CASES = [
 ]
 
 
-def _case_tensors(case):
-    k, c0, c1, cout, n, h, w = case
-    rng = np.random.Generator(np.random.PCG64(2077 + k * 1000 + c0 + 3 * c1 + cout + 7 * h + w))
-    x0 = _rand(rng, (n, c0, h, w))
-    x1 = _rand(rng, (n, c1, h, w)) if c1 else None
-    cin = c0 + c1
-    wt = _rand(rng, (cout, cin, k, k), 1.5 / np.sqrt(cin * k * k))
-    b = _rand(rng, (cout,), 0.1)
-    return x0, x1, wt, b
-
-
 def test_the_oracle_stays_affordable():
     """No layer case costs the oracle more than the largest of test_slomo_gpu.S3_CASES (7x7 32 -> 32 at 256 x 320)."""
     for k, c0, c1, cout, n, h, w in H2_CASES + H2_FALLBACK_CASES:
@@ -184,6 +99,7 @@ def test_two_piece_conv_layer_matches_oracle(case, oracle_lib):
         case, "" if has_tile else " [f32 fallback]", e_ref, e_32, relerr(y32, ref), relerr(y3, ref), layer.sl2))
     assert e_ref < TOL
     assert e_32 < TOL
+    assert relerr(y3, ref) < TOL
     if has_tile:   # it is not the same kernel three times
         assert not np.array_equal(y, y32) and not np.array_equal(y, y3)
     else:          # by design: the very kernel the f32 math runs
