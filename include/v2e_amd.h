@@ -339,6 +339,12 @@ int v2e_emu_event_writer(v2e_emu *h);
  * per launch, state in registers; records from k_ahead), 4 = k_chain with the per-frame records built inside the chain;
  * frames_per_launch of the dependency chain and frames per emission batch. */
 int v2e_emu_last_pipeline(v2e_emu *h, int *kind, int *frames_per_launch, int *frames_per_batch);
+/* What the schedule of the last v2e_emu_run through k_chain put on the caller's stream: out = {kernel launches, stream waits, event
+ * records} (a graph run: what its capture held).  A pipelined run's schedule puts the chain's launches there, one wait for the run's
+ * head plus one per batch where the ring wraps, and no record: every event that says "this chain launch has finished" is that
+ * launch's stop event.  (Not the schedule's and not counted: without V2E_RUN_FRAMES_RESIDENT one record IN FRONT of the run orders
+ * its head behind the caller's earlier work.)  Fails where the last run had no k_chain. */
+int v2e_emu_last_run_queue_ops(v2e_emu *h, int out[3]);
 
 /* ------------------------------------------------------------- SuperSloMo */
 

@@ -26,6 +26,7 @@
 // modes and the dev tools.
 #include "common.h"
 #include "../../include/v2e_detmath.h"
+#include <hip/hip_ext.h> // hipExtLaunchKernel: a kernel launch with a stop event (emu_chain_host.h)
 
 #include <cstdarg>
 #include <cstdlib>
@@ -797,9 +798,9 @@ static int run_pipelined(v2e_emu *h, const v2e_emu_params *p, const KArgs &a, co
         V2E_HIP(hipStreamWaitEvent(s_up, h->ev_tail_done2[par ^ 1], 0));
     int rc = upload_run(h, p, n_frames, t_prev, t_frame, frame_idx0, frames, s_up);
     if (rc) return rc;
-    rc = enqueue_run_chain(h, p, a, dtype, n_frames, events, cap, recs_dev, s, ChainMode::pipelined);
+    // ev_main_done2[par], the run's chain (the pixel state): the stop event of its last chain launch, not a record behind it
+    rc = enqueue_run_chain(h, p, a, dtype, n_frames, events, cap, recs_dev, s, ChainMode::pipelined, nullptr, h->ev_main_done2[par]);
     if (rc) return rc;
-    V2E_HIP(hipEventRecord(h->ev_main_done2[par], s)); // the run's chain (the pixel state)
     hipStream_t rows_stream = h->side2;
     // the run's records to pinned host memory behind its last rows (v2e_emu_run_recs): what result() reads -- no copy of the
     // caller's own, no stream of the caller's to synchronise
@@ -913,7 +914,7 @@ static int run_graph(v2e_emu *h, const v2e_emu_params *p, const KArgs &a, const 
     std::vector<unsigned char> key = graph_key(h, p, a, frames, dtype, n_frames, events, cap, recs_dev, chain);
     hipGraphExec_t exec = nullptr;
     for (auto &cg : h->graphs)
-        if (cg.key == key) { exec = cg.exec; cg.used = ++h->graph_clock; break; }
+        if (cg.key == key) { exec = cg.exec; cg.used = ++h->graph_clock; memcpy(h->last_queue_ops, cg.ops, sizeof(cg.ops)); break; }
     if (!exec) {
         if (h->graphs.size() >= 24) { // (two scratch sets x the caller's buffer sets)
             size_t lru = 0;
@@ -933,7 +934,7 @@ static int run_graph(v2e_emu *h, const v2e_emu_params *p, const KArgs &a, const 
         V2E_HIP(e);
         V2E_HIP(hipGraphInstantiate(&exec, g, nullptr, nullptr, 0));
         V2E_HIP(hipGraphDestroy(g));
-        h->graphs.push_back({std::move(key), exec, ++h->graph_clock});
+        h->graphs.push_back({std::move(key), exec, ++h->graph_clock, {h->last_queue_ops[0], h->last_queue_ops[1], h->last_queue_ops[2]}});
     }
     V2E_HIP(hipGraphLaunch(exec, s));
     return 0;
@@ -1131,6 +1132,14 @@ int v2e_emu_last_pipeline(v2e_emu *h, int *kind, int *frames_per_launch, int *fr
 {
     V2E_REQUIRE(h && kind && frames_per_launch && frames_per_batch, "null");
     *kind = h->last_kind; *frames_per_launch = h->last_fpl; *frames_per_batch = h->last_fpb;
+    return 0;
+}
+
+int v2e_emu_last_run_queue_ops(v2e_emu *h, int out[3])
+{
+    V2E_REQUIRE(h && out, "null");
+    V2E_REQUIRE(h->last_kind >= 3, "the last run did not go through k_chain");
+    memcpy(out, h->last_queue_ops, sizeof(h->last_queue_ops));
     return 0;
 }
 

@@ -11,9 +11,16 @@ enum { EV_FORK = 0, EV_JOIN = 1, EV_AHEAD = 2, EV_CHAIN = 3, EV_TAB = 4 };
 struct Sched {
     v2e_emu *h;
     hipStream_t st[ST_COUNT];
+    // Pipelined runs: an event that would be recorded on the chain's stream right behind a chain launch is that launch's STOP EVENT
+    // instead (hipExtLaunchKernel: bound to the kernel's own dispatch, no packet of its own in the queue); where several events
+    // follow one launch, one is the stop event and stands in for the others this run (stand_in: their waiters wait for it).
+    struct StandIn { int kind, idx; hipEvent_t ev; };
+    std::vector<StandIn> stand_in;
+    int ops[3] = {0, 0, 0}; // launches, waits, records this run put on ST_MAIN (v2e_emu_last_run_queue_ops)
 
     hipEvent_t real_event(int kind, int idx) const
     {
+        for (const StandIn &a : stand_in) if (a.kind == kind && a.idx == idx) return a.ev;
         switch (kind) {
         case EV_FORK: return h->ev_fork[idx];
         case EV_JOIN: return h->ev_join[idx];
@@ -22,9 +29,11 @@ struct Sched {
         default: return h->ev_tab[idx];
         }
     }
-    int kernel(int s, const void *fn, dim3 grid, dim3 block, size_t lds, void **args)
+    int kernel(int s, const void *fn, dim3 grid, dim3 block, size_t lds, void **args, hipEvent_t stop = nullptr)
     {
-        V2E_HIP(hipLaunchKernel(fn, grid, block, args, lds, st[s]));
+        if (stop) V2E_HIP(hipExtLaunchKernel(fn, grid, block, args, lds, st[s], nullptr, stop, 0));
+        else V2E_HIP(hipLaunchKernel(fn, grid, block, args, lds, st[s]));
+        ops[0] += s == ST_MAIN;
         return 0;
     }
     int zero4(int s, void *const ptr[4], const size_t bytes[4])
@@ -39,11 +48,13 @@ struct Sched {
     int record(int kind, int idx, int s)
     {
         V2E_HIP(hipEventRecord(real_event(kind, idx), st[s]));
+        ops[2] += s == ST_MAIN;
         return 0;
     }
     int wait(int s, int kind, int idx)
     {
         V2E_HIP(hipStreamWaitEvent(st[s], real_event(kind, idx), 0));
+        ops[1] += s == ST_MAIN;
         return 0;
     }
 };
@@ -58,10 +69,14 @@ static bool chain_small_grid(const v2e_emu *h) { return (long long)h->ngroups * 
 // and 1280x720 do not care (14.5-14.6 / 11.9-12.1 Gev/s either way) -- but PIPELINED runs of a small grid, whose k_ahead runs a whole
 // run ahead and whose event rows have a stream of their own, gain from never waiting inside a 300-frame run: ring 3 681-685 us per
 // step, 4 668-671, 5 662-664, 6 657-673, 8 671 (profiles/r06_emulator_experiments.txt item 21).  A handle keeps the depth its FIRST
-// device-resident run chose (no re-allocation when a caller mixes modes).
+// device-resident run chose (no re-allocation when a caller mixes modes).  V2E_AMD_CHAIN_RING=3..8 overrides that choice (dev / tests:
+// a pipelined 300-frame run in a ring of three batches wraps, so its chain and k_ahead wait for one another batch by batch).
 static int chain_ring_batches(v2e_emu *h, bool pipelined)
 {
-    if (h->ch_ring_pref == 0) h->ch_ring_pref = (pipelined && chain_small_grid(h) && h->n_clips == 1) ? 5 : 3;
+    if (h->ch_ring_pref == 0) {
+        h->ch_ring_pref = (pipelined && chain_small_grid(h) && h->n_clips == 1) ? 5 : 3;
+        if (const char *ev = getenv("V2E_AMD_CHAIN_RING")) { const int v = atoi(ev); if (v >= 3 && v <= 8) h->ch_ring_pref = v; }
+    }
     return h->ch_ring_pref;
 }
 
@@ -340,7 +355,8 @@ enum class ChainMode {
 struct ChainMarks { std::vector<hipEvent_t> chain, rows; }; // the events of a profiled run, in pairs (before, after)
 
 static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a_in, int dtype, int n_frames, float *events,
-                             uint64_t cap, v2e_frame_rec *recs, hipStream_t s, ChainMode mode, ChainMarks *marks = nullptr)
+                             uint64_t cap, v2e_frame_rec *recs, hipStream_t s, ChainMode mode, ChainMarks *marks = nullptr,
+                             hipEvent_t run_done = nullptr) // pipelined: completes with the run's last chain launch
 {
     // Three logical streams: the chain (k_chain, K frames per launch); k_ahead and the emission tables (k_ctot, k_cframe);
     // the event writer k_cemit; the last two in batches of E = m K frames (batch b = frames [b E, (b + 1) E) = chain
@@ -576,10 +592,24 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
         if (!ahead_whole && pl.wait_ahead >= 0 && sc.wait(ST_MAIN, EV_AHEAD, pl.wait_ahead)) return V2E_EHIP;
         if (split0 && !fused_rec && !tail && L >= 1 && L < m && sc.wait(ST_MAIN, EV_AHEAD, nL)) return V2E_EHIP; // the rest of batch 0
         if (mark(false, s)) return V2E_EHIP; // profiled runs: an event before and after every chain launch
+        // Pipelined: whatever would be recorded behind this launch -- the run's end, the emission batch it makes final, what a later
+        // k_ahead batch waits for where the ring wraps -- is its stop event: the chain's queue holds launches and waits only (a record
+        // there cost the next launch 2.4 us, and its waiter 3.8 us more: profiles/r24_chain_queue_packets.txt)
+        const bool rec_chain = !ahead_whole && !fused_rec && L % m == 0;
+        hipEvent_t stop = nullptr;
+        if (pipelined) {
+            auto follows = [&](int kind, int idx) {
+                if (!stop) stop = sc.real_event(kind, idx);
+                else sc.stand_in.push_back({kind, idx, stop});
+            };
+            if (L == nL - 1) stop = run_done;
+            if (pl.emit_batch >= 0) follows(EV_FORK, pl.emit_batch);
+            if (rec_chain) follows(EV_CHAIN, L);
+        }
         void *args[] = {(void *)&a, (void *)&ca};
-        if (sc.kernel(ST_MAIN, kfn, grid, dim3(BLOCK), 0, args)) return V2E_EHIP;
+        if (sc.kernel(ST_MAIN, kfn, grid, dim3(BLOCK), 0, args, stop)) return V2E_EHIP;
         if (mark(false, s)) return V2E_EHIP;
-        if (!ahead_whole && !fused_rec && L % m == 0 && sc.record(EV_CHAIN, L, ST_MAIN)) return V2E_EHIP; // (what a later k_ahead batch waits for where the ring wraps)
+        if (!pipelined && rec_chain && sc.record(EV_CHAIN, L, ST_MAIN)) return V2E_EHIP; // (what a later k_ahead batch waits for where the ring wraps)
         // k_ahead before the emission: the enqueue order decides how this runtime executes the captured graph -- with the emission
         // first the chain's next launch runs BEHIND the emission kernels, with k_ahead first beside them (profiles/r03_graph_scheduling.txt)
         if (!ahead_whole && pl.ahead_next >= 0) { if (launch_ahead(pl.ahead_next)) return V2E_EHIP; last_ahead = pl.ahead_next; }
@@ -595,7 +625,7 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
         } else if (pl.emit_batch >= 0) {
             // (emitting the batches in PAIRS -- one record on the chain's stream per 128 frames -- was measured in round 6: gaps inside a run
             //  54 -> 46 us, but the bunched emission costs the chain's launches more than that: 614-633 -> 628-641 us per step)
-            if (sc.record(EV_FORK, pl.emit_batch, ST_MAIN)) return V2E_EHIP;
+            if (!pipelined && sc.record(EV_FORK, pl.emit_batch, ST_MAIN)) return V2E_EHIP;
             if (launch_emission(pl.emit_batch, pl.emit_batch * E, std::min((pl.emit_batch + 1) * E, n_frames) - pl.emit_batch * E)) return V2E_EHIP;
             last_emitted = pl.emit_batch;
         }
@@ -607,6 +637,7 @@ static int enqueue_run_chain(v2e_emu *h, const v2e_emu_params *p, const KArgs &a
         if (!fused_rec && last_ahead >= 0 && sc.wait(ST_MAIN, EV_AHEAD, last_ahead)) return V2E_EHIP;
     }
     V2E_HIP(hipGetLastError());
+    memcpy(h->last_queue_ops, sc.ops, sizeof(sc.ops));
     return 0;
 }
 

@@ -174,7 +174,7 @@ struct v2e_emu {
     }
     // ---- graphs: captured runs, keyed by everything baked into them (buffers, sizes, parameters): a caller that alternates between
     // two sets of frame / event / record buffers (the asynchronous API) replays two graphs
-    struct CachedGraph { std::vector<unsigned char> key; hipGraphExec_t exec; unsigned long long used; };
+    struct CachedGraph { std::vector<unsigned char> key; hipGraphExec_t exec; unsigned long long used; int ops[3]; };
     std::vector<CachedGraph> graphs;
     unsigned long long graph_clock = 0;
     void drop_graphs()
@@ -188,7 +188,8 @@ struct v2e_emu {
     std::vector<float> prof_chain_us; // the chain launches of the last instrumented run, one by one
     int prof_emit_batches = 0, prof_step_launches = 0;
     int last_kind = -1, last_fpl = 0, last_fpb = 0; // v2e_emu_last_pipeline
-    int ch_last_launches = 0;       // chain launches of the last run with a refractory period (their rule-on rows: v2e_emu_debug_chain_rows), 0 otherwise
+    int last_queue_ops[3] = {0, 0, 0}; // launches, waits, records the last k_chain run put on the caller's stream (v2e_emu_last_run_queue_ops)
+    int ch_last_launches = 0;      // chain launches of the last run with a refractory period (their rule-on rows: v2e_emu_debug_chain_rows), 0 otherwise
     // per-launch device time stamps of the chain kernel (v2e_emu_launch_stamps): [runs_cap][STAMP_LAUNCHES][2] wall-clock words
     unsigned long long *stamps = nullptr;
     int stamps_runs = 0;                       // runs the buffer holds (0: off)

@@ -436,6 +436,12 @@ class EmuEngine:
         names = {0: "k_count/k_rank/k_scan/k_emit", 3: "k_chain", 4: "k_chain(fused records)"}
         return names.get(k.value, "?"), a.value, b.value
 
+    def last_run_queue_ops(self):
+        """(launches, waits, records) the last k_chain run() put on the caller's stream; see v2e_emu_last_run_queue_ops."""
+        out = (C.c_int * 3)()
+        check(self.lib.v2e_emu_last_run_queue_ops(self._h, out), "v2e_emu_last_run_queue_ops")
+        return tuple(int(v) for v in out)
+
     def alloc_recs(self, n_frames, which=0):
         """Device record array [F][n_clips] (struct v2e_frame_rec = 32 bytes), cached per (F, set) so that
         the hipGraph of run() (which bakes the pointer in) stays valid across calls."""
