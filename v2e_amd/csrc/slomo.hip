@@ -3,8 +3,9 @@
 // Reference (SensorsINI/v2e): v2ecore/model.py:10-226 (UNet/down/up), :229-300 (backWarp),
 // v2ecore/slomo.py:338-345 (flow UNet), :404-433 (per-t blend, 4 warps, interp UNet, fusion).
 //
-// One translation unit: slomo_conv.h (the convolution arguments, the range slots, the f32 matrix-core kernel), slomo_s3.h and
-// slomo_s3p.h (the split-operand kernels), slomo_stream.h (pooling, upsampling, prep, fuse and the other streaming kernels); here
+// One translation unit: slomo_conv.h (the convolution arguments, the range slots, the f32 matrix-core kernel), slomo_tile.h (the
+// steps the convolution kernels share beside their multiplies: tile decode, concat source, staging plan, epilogue, grid), slomo_s3.h
+// and slomo_s3p.h (the split-operand kernels), slomo_stream.h (pooling, upsampling, prep, fuse and the other streaming kernels); here
 // the tile selection of the split-operand kernels, one layer, the UNet pass and the C entry points.
 #include "common.h"
 #include <cstdlib>

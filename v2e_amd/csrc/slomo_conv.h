@@ -102,20 +102,18 @@ __device__ __forceinline__ void act_scale(const ConvArgs &a, float &in_scale, fl
     inv = __uint_as_float((uint32_t)(127 - k) << 23);
 }
 
+#include "slomo_tile.h"
+
 // element fetch with the producer op fused: PRE 0 plain, 1 avg_pool2d(2) of a [2H][2W] source,
 // 2 bilinear x2 upsample (align_corners=False) of a [H/2][W/2] source.
 template <int PRE>
 __device__ __forceinline__ float fetch(const ConvArgs &a, int n, int c, int gy, int gx)
 {
-    const float *src;
-    int cs, C;
-    if (c < a.c0) { src = a.x0; cs = c; C = a.c0; }
-    else { src = a.x1; cs = c - a.c0; C = a.c1; }
     if (PRE == 0) {
-        return src[(((size_t)n * C + cs) * a.h + gy) * a.w_ + gx];
+        return concat_chunk(a, c, n, a.h * a.w_)[gy * a.w_ + gx];
     } else if (PRE == 1) { // F.avg_pool2d(x, 2): (((a+b)+c)+d) / 4
         const int sw = 2 * a.w_;
-        const float *p = src + (((size_t)n * C + cs) * (2 * a.h) + 2 * gy) * sw + 2 * gx;
+        const float *p = concat_chunk(a, c, n, 2 * a.h * sw) + 2 * gy * sw + 2 * gx;
         return (((p[0] + p[1]) + p[sw]) + p[sw + 1]) * 0.25f;
     } else { // F.interpolate(scale_factor=2, mode='bilinear', align_corners=False)
         const int sh = a.h >> 1, sw = a.w_ >> 1;
@@ -127,7 +125,7 @@ __device__ __forceinline__ float fetch(const ConvArgs &a, int n, int c, int gy, 
         const int y1 = y0 + (y0 < sh - 1 ? 1 : 0), x1 = x0 + (x0 < sw - 1 ? 1 : 0);
         const float ly = ry - (float)y0, lx = rx - (float)x0;
         const float hy = 1.f - ly, hx = 1.f - lx;
-        const float *p = src + ((size_t)n * C + cs) * sh * sw;
+        const float *p = concat_chunk(a, c, n, sh * sw);
         return hy * (hx * p[y0 * sw + x0] + lx * p[y0 * sw + x1]) + ly * (hx * p[y1 * sw + x0] + lx * p[y1 * sw + x1]);
     }
 }
@@ -158,12 +156,9 @@ __global__ __launch_bounds__(WP * 64) void k_conv(ConvArgs a)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hsel = lane >> 5, l31 = lane & 31;
-    int bx = blockIdx.x;
-    const int tx_i = bx % a.tiles_x; bx /= a.tiles_x;
-    const int ty_i = bx % a.tiles_y;
-    const int n = (bx / a.tiles_y) * STK; // first sample of the tile
-    const int oy0 = ty_i * TH, ox0 = tx_i * TW;
-    const int cobase = blockIdx.y * COT;
+    ConvTile tile; // (the grid is 2-D: no padding workgroups)
+    conv_tile<TH, TW, COT, STK>(a, tile);
+    const int n = tile.n, oy0 = tile.oy0, ox0 = tile.ox0, cobase = tile.cobase;
     const int hw = a.h * a.w_;
     const bool vecw = (a.cout & 3) == 0; // float4 weight rows (every layer but the 4/5-channel heads)
 
@@ -213,12 +208,7 @@ __global__ __launch_bounds__(WP * 64) void k_conv(ConvArgs a)
     }
 
     f32x16 acc[CT][PT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int pt = 0; pt < PT; ++pt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ct][pt][r] = 0.f;
+    acc_zero(acc);
 
     float pv[NPE];
     float4 wv[NWE];
@@ -226,15 +216,12 @@ __global__ __launch_bounds__(WP * 64) void k_conv(ConvArgs a)
     auto prefetch = [&](int cb) {
         if (PRE == 0) {
             // all CI_T channels of a chunk come from one concat source (c0 is a multiple of CI_T)
-            const float *src;
-            int cs, C;
-            if (cb < a.c0) { src = a.x0; cs = cb; C = a.c0; }
-            else { src = a.x1; cs = cb - a.c0; C = a.c1; }
-            const float *base = src + ((size_t)n * C + cs) * hw;
+            const float *base = concat_chunk(a, cb, n, hw);
+            const float *base1 = STK == 2 ? concat_chunk(a, cb, n + 1, hw) : base; // the tile's second sample
 #pragma unroll
             for (int j = 0; j < NPE; ++j) {
                 const int pi = pinfo[j];
-                if (STK == 2) pv[j] = pi >= 0 ? base[(size_t)(pi & 0x3FFFFFFF) + (size_t)(pi >> 30) * C * hw] : 0.f;
+                if (STK == 2) pv[j] = pi >= 0 ? (pi >> 30 ? base1 : base)[pi & 0x3FFFFFFF] : 0.f;
                 else pv[j] = pi >= 0 ? base[pi] : 0.f;
             }
         } else {
@@ -302,7 +289,8 @@ __global__ __launch_bounds__(WP * 64) void k_conv(ConvArgs a)
             }
         }
     }
-    // epilogue: bias + leaky_relu(0.1); register r of lane: channel (r&3)+8(r>>2)+4*hsel, pixel l31
+    // epilogue: conv_store's, with the second sample of a stacked tile and cout that is no multiple of 32.  Its own copy: through
+    // conv_store / acc_channel the two five-wave PRE = 1 instantiations took 105 VGPRs instead of 95 (occupancy 5 -> 4)
     uint32_t omax = 0u;
 #pragma unroll
     for (int pt = 0; pt < PT; ++pt) {
@@ -316,8 +304,7 @@ __global__ __launch_bounds__(WP * 64) void k_conv(ConvArgs a)
             for (int r = 0; r < 16; ++r) {
                 const int ch = cobase + ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
                 if (pok && ch < a.cout) {
-                    float v = acc[ct][pt][r] + a.bias[ch];
-                    v = v > 0.f ? v : v * 0.1f;
+                    const float v = lrelu_bias(acc[ct][pt][r], a.bias[ch]);
                     amax_fold(omax, v);
                     a.y[(((size_t)(n + sidx) * a.cout + ch) * a.h + oy) * a.w_ + ox] = v;
                 }
@@ -332,11 +319,7 @@ template <int KS, int CI_T, int CT, int PT, int WP, int TW, int PRE>
 static void launch_conv(const ConvArgs &a0, hipStream_t s)
 {
     ConvArgs a = a0;
-    constexpr int TH = WP * PT * 32 / TW;
-    a.tiles_x = (a.w_ + TW - 1) / TW;
-    a.tiles_y = (a.h + TH - 1) / TH;
-    dim3 grid((unsigned)(a.n * a.tiles_x * a.tiles_y), (unsigned)((a.cout + CT * 32 - 1) / (CT * 32)));
-    k_conv<KS, CI_T, CT, PT, WP, TW, PRE><<<grid, WP * 64, 0, s>>>(a);
+    launch_tiles<k_conv<KS, CI_T, CT, PT, WP, TW, PRE>>(a, WP * PT * 32 / TW, TW, (a.cout + CT * 32 - 1) / (CT * 32), false, WP * 64, 0, s);
 }
 
 // two whole samples per tile (sample height == half the tile height)

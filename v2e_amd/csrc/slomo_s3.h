@@ -133,7 +133,6 @@ void k_conv_s3(ConvArgs a)
 {
     constexpr bool PADC = MODE == 1, PRES = MODE == 2;
     constexpr int NT = WP * 64;
-    constexpr int PAD = KS / 2;
     constexpr int NPX = WP * PT * 32;
     constexpr int TH = NPX / TW;
     constexpr int PH = TH + KS - 1, PW = TW + KS - 1, PP = PH * PW;
@@ -153,28 +152,14 @@ void k_conv_s3(ConvArgs a)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hsel = lane >> 5, l31 = lane & 31;
-    // workgroup -> (pixel tile, channel block).  Workgroups go to the 8 XCDs round-robin by linear id and each XCD has its
-    // own L2, so the channel blocks of ONE pixel tile are consecutive on ONE XCD (ids L, L+8, L+16, ...): the tile's input
-    // patch crosses the fabric once instead of once per channel block, and since the workgroups of an XCD walk the
-    // input-channel chunks roughly in step, the weight slices they share stay L2-resident too (measured: DESIGN.md 4).
-    int bx, cblk;
-    if (a.ncb > 0) {
-        const int L = blockIdx.x, j = L >> 3;
-        cblk = j % a.ncb;
-        bx = (j / a.ncb) * 8 + (L & 7);
-        if (bx >= a.n * a.tiles_x * a.tiles_y) return; // padding of the last group of 8 pixel tiles
-    } else {
-        bx = blockIdx.x;
-        cblk = blockIdx.y;
-    }
-    const int tx_i = bx % a.tiles_x; bx /= a.tiles_x;
-    const int ty_i = bx % a.tiles_y;
-    const int n = bx / a.tiles_y;
-    const int oy0 = ty_i * TH, ox0 = tx_i * TW;
-    const int cobase = cblk * COT;
+    ConvTile tile; // workgroup -> (pixel tile, channel block)
+    if (!conv_tile<TH, TW, COT>(a, tile)) return;
+    const int n = tile.n, oy0 = tile.oy0, ox0 = tile.ox0, cobase = tile.cobase;
     const int hw = a.h * a.w_;
     const u32x4 *wsrc = (const u32x4 *)a.ws3;
 
+    // (the lane's operand offsets at tap (0, 0) stay here and in k_conv_s3p: built in s3_plan, k_conv_s3<5,2,2,4,32,1,0,1,2> came out with
+    // its kernel-row loop unrolled by 5: 300 MFMAs in the listing instead of 60)
     int bofs[PT];
 #pragma unroll
     for (int pt = 0; pt < PT; ++pt) {
@@ -182,38 +167,12 @@ void k_conv_s3(ConvArgs a)
         bofs[pt] = hsel * PP + (m / TW) * PW + (m % TW);
     }
     const int aofs = hsel * COT + l31;
-
-    int pinfo[NPI]; // first channel of the item: offset inside one sample's chunk, or -1 (zero padding / unused)
-    int pcig[NPI];  // PADC: the item's channel group (0 / 1)
-#pragma unroll
-    for (int j = 0; j < NPI; ++j) {
-        const int i = tid + j * NT;
-        int v = -1;
-        pcig[j] = i < PP ? 0 : 1;
-        if (i < 2 * PP) {
-            const int cig = i / PP, r = i - cig * PP;
-            const int py = r / PW, px = r - py * PW;
-            const int gy = oy0 + py - PAD, gx = ox0 + px - PAD;
-            if (gy >= 0 && gy < a.h && gx >= 0 && gx < a.w_) v = cig * (PRES ? 1 : 8) * hw + gy * a.w_ + gx; // PRES: 16-byte units
-        }
-        pinfo[j] = v;
-    }
-    int woff[NWU]; // unit -> offset inside one group's weight block (units)
-#pragma unroll
-    for (int j = 0; j < NWU; ++j) {
-        const int u = tid + j * NT;
-        const int uu = u < WU ? u : WU - 1; // surplus threads load a valid unit and do not store it
-        const int r = uu / COT, c = uu - r * COT;
-        woff[j] = r * a.cout + cobase + c;
-    }
+    int pinfo[NPI], woff[NWU]; // the staging plan: slomo_tile.h
+    s3_plan<KS, WP, PT, TW, COT, WU, PRES>(a, tile, pinfo, woff);
+    const auto pcig = [&](int j) { return tid + j * NT < PP ? 0 : 1; }; // PADC: the channel group (0 / 1) of patch item j
 
     f32x16 acc[CT][PT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int pt = 0; pt < PT; ++pt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ct][pt][r] = 0.f;
+    acc_zero(acc);
 
     // global -> register prefetch, DEEP chunks ahead.  A fetch round trip is ~4 us under load and one chunk of a
     // 3x3 layer is ~2.4 us of multiplies, so the 3x3 kernels (one weight group per chunk) keep TWO chunks in flight
@@ -234,17 +193,13 @@ void k_conv_s3(ConvArgs a)
             }
             return;
         }
-        const float *src;
-        int cs, C;
-        if (cb < a.c0) { src = a.x0; cs = cb; C = a.c0; }
-        else { src = a.x1; cs = cb - a.c0; C = a.c1; }
-        const float *base = src + ((size_t)n * C + cs) * hw;
+        const float *base = concat_chunk(a, cb, n, hw);
 #pragma unroll
         for (int j = 0; j < NPI; ++j) {
             const int pi = pinfo[j];
             const float *q = base + (pi < 0 ? 0 : pi);
             if (PADC) { // channels beyond cin: read the last valid one (zeroed when staged)
-                const int nv = a.cin - cb - pcig[j] * 8; // valid channels of this item (may be <= 0: all padding)
+                const int nv = a.cin - cb - pcig(j) * 8; // valid channels of this item (may be <= 0: all padding)
                 if (nv <= 0) q = base;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) pv[set][j][e] = q[(size_t)(nv <= 0 ? 0 : (e < nv ? e : nv - 1)) * hw];
@@ -278,7 +233,7 @@ void k_conv_s3(ConvArgs a)
                 }
             } else if (i < 2 * PP) {
                 const bool ok = pinfo[j] >= 0;
-                const int nv = PADC ? a.cin - cbs - pcig[j] * 8 : 8;
+                const int nv = PADC ? a.cin - cbs - pcig(j) * 8 : 8;
                 uint32_t q[NP][4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -396,32 +351,9 @@ void k_conv_s3(ConvArgs a)
     if constexpr (NP == 2) {
         if (a.ovf && in_bad && tid == 0) atomicOr(a.ovf, 1);
     }
-    uint32_t omax = 0u;
     // the two scale factors as ONE multiply: act_scale keeps 2^-(k + s) a normal float32, so the product is exact
     const float os1 = NP == 2 ? a.out_scale * inv_scale : 1.0f;
-    // epilogue as k_conv: register r of a lane is channel (r&3)+8(r>>2)+4*hsel of pixel l31
-#pragma unroll
-    for (int pt = 0; pt < PT; ++pt) {
-        const int m = (wave * PT + pt) * 32 + l31;
-        const int oy = oy0 + m / TW, ox = ox0 + (m % TW);
-        const bool pok = oy < a.h && ox < a.w_;
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ch = cobase + ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
-                if (pok) {
-                    float s = acc[ct][pt][r];
-                    if constexpr (NP == 2) s *= os1; // the powers of two the operands were staged times, divided out (exact)
-                    float v = s + a.bias[ch];
-                    v = v > 0.f ? v : v * 0.1f;
-                    amax_fold(omax, v);
-                    a.y[(((size_t)n * a.cout + ch) * a.h + oy) * a.w_ + ox] = v;
-                }
-            }
-        }
-    }
-    if (a.am_out) amax_commit(a.am_out, omax);
+    conv_store<TW>(a, tile, acc, os1);
     // avg_pool2d(2) of what was just written (model.py:96: the next block's input), in k_avgpool2's order of additions:
     // ((row0[x] + row0[x + 1]) + row1[x]) + row1[x + 1], times 0.25.  A wave of these tiles holds rows 2 wave, 2 wave + 1 of the
     // tile (pt 0 / 1), a lane one pixel of each: the window is the lane's two registers and its odd neighbour's.
@@ -434,15 +366,8 @@ void k_conv_s3(ConvArgs a)
             for (int ct = 0; ct < CT; ++ct) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int ch = cobase + ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
-                    float v[2];
-#pragma unroll
-                    for (int pt = 0; pt < 2; ++pt) { // the stored value, recomputed from the accumulator (same operations)
-                        float sacc = acc[ct][pt][r];
-                        if constexpr (NP == 2) sacc *= os1;
-                        float t = sacc + a.bias[ch];
-                        v[pt] = t > 0.f ? t : t * 0.1f;
-                    }
+                    const int ch = cobase + acc_channel(ct, r);
+                    const float v[2] = {lrelu_bias(acc[ct][0][r] * os1, a.bias[ch]), lrelu_bias(acc[ct][1][r] * os1, a.bias[ch])}; // as stored
                     const float n0 = __shfl_xor(v[0], 1), n1 = __shfl_xor(v[1], 1);
                     const float o = (((v[0] + n0) + v[1]) + n1) * 0.25f;
                     if (st) a.ypool[(((size_t)n * a.cout + ch) * ph + (oy >> 1)) * pw + (ox >> 1)] = o;
@@ -463,19 +388,10 @@ static int launch_conv_s3(const ConvArgs &a0, hipStream_t s, LayerCtx &ctx)
     ctx.pooled = TW == 32 && PT == 2 && ctx.pool_out && a.h % 2 == 0 && a.w_ % 2 == 0; // the tile that can write the pooled copy
     a.ypool = ctx.pooled ? ctx.pool_out : nullptr;
     static_assert(lds <= 160 * 1024, "LDS");
-    static bool attr_set = false; // one per instantiation
-    if (!attr_set) {
-        V2E_HIP(hipFuncSetAttribute((const void *)k_conv_s3<KS, CT, PT, WP, TW, NB, MODE, RG, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    a.tiles_x = (a.w_ + TW - 1) / TW;
-    a.tiles_y = (a.h + TH - 1) / TH;
-    constexpr int order = 1; // channel blocks of a pixel tile consecutive (round 2; 0 = pixel tiles fastest measured slower)
-    const int ntiles = a.n * a.tiles_x * a.tiles_y, ncb = a.cout / (CT * 32);
-    // measured at 40 samples: +6 % where a pixel tile has >= 4 channel blocks (256->128 at 64x80, 512->256 at 32x40), within
-    // noise at 2 blocks, -3 % on the five-wave 20-wide tiles (16 blocks: more workgroups than an XCD holds at once)
-    a.ncb = ((order == 1 && KS == 3 && WP == 4 && ncb >= 4) || (order == 2 && ncb > 1)) ? ncb : 0;
-    dim3 grid = a.ncb ? dim3((unsigned)((ntiles + 7) / 8 * 8 * ncb)) : dim3((unsigned)ntiles, (unsigned)ncb);
-    k_conv_s3<KS, CT, PT, WP, TW, NB, MODE, RG, NP><<<grid, WP * 64, lds, s>>>(a);
-    return 0;
+    const int ncb = a.cout / (CT * 32);
+    // channel blocks of a pixel tile consecutive (round 2; pixel tiles fastest measured slower).  Measured at 40 samples: +6 % where
+    // a pixel tile has >= 4 channel blocks (256->128 at 64x80, 512->256 at 32x40), within noise at 2 blocks, -3 % on the five-wave
+    // 20-wide tiles (16 blocks: more workgroups than an XCD holds at once)
+    const bool xcd_order = KS == 3 && WP == 4 && ncb >= 4;
+    return launch_tiles<k_conv_s3<KS, CT, PT, WP, TW, NB, MODE, RG, NP>>(a, TH, TW, ncb, xcd_order, WP * 64, lds, s);
 }

@@ -25,21 +25,16 @@
 // pair so that every buffer and register-set index is a compile-time constant), plain f32 NCHW input (one or two concat
 // sources with channel counts that are multiples of 16).  Everything else stays on k_conv_s3.
 
-// DBG (the ablation of round 3: instantiate launch_conv_s3p<16, DBG> in conv_dispatch_s3p to repeat it -- the environment switch that
-// selected it is gone; results are wrong by construction): 1 = no side work
-// (what the multiplies, their operand reads and the barriers cost alone), bit 2 (4) = no global reloads, bit 3 (8) = no LDS
-// stores, 16 = no splitting arithmetic, 32 = no operand reads of the next tap, 64 / 128 = no patch / weight reloads; 2 = no
-// multiplies.  The per-step timeline below works in every mode.  Measured (profiles/r03_slomo_s3p_ablation.txt): the kernel is
-// at the chip's POWER limit -- fewer clocks per step lower the shader clock (1.63-1.86 GHz of 2.4) and leave the step's wall
-// time where it was; what saves time is what saves energy per multiply (LDS and global bytes), not issue slots.
+// What bounds it is the chip's power limit, not issue slots: profiles/r03_slomo_s3p_ablation.txt (the ablation switches that
+// measured it, a DBG template parameter, are in the history of this file for anyone who wants to repeat it).
 __device__ unsigned long long g_s3p_timeline[2 * 512]; // dev: (shader clock, 100 MHz wall clock) at every step of workgroup 0
 static int g_s3p_timeline_on = 0; // host: passed to the kernel as an argument (ConvArgs::tl_on)
 
-template <int TW, int DBG = 0>
+template <int TW>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_conv_s3p(ConvArgs a)
 {
-    constexpr int CT = 2, PT = 2, WP = 4, NT = 256, KS = 3, PAD = 1;
+    constexpr int CT = 2, PT = 2, WP = 4, NT = 256, KS = 3;
     constexpr int NPX = WP * PT * 32;
     constexpr int TH = NPX / TW;
     constexpr int PH = TH + KS - 1, PW = TW + KS - 1, PP = PH * PW;
@@ -54,21 +49,9 @@ void k_conv_s3p(ConvArgs a)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hsel = lane >> 5, l31 = lane & 31;
-    int bx, cblk; // (see k_conv_s3: channel blocks of one pixel tile consecutive on one XCD)
-    if (a.ncb > 0) {
-        const int L = blockIdx.x, j = L >> 3;
-        cblk = j % a.ncb;
-        bx = (j / a.ncb) * 8 + (L & 7);
-        if (bx >= a.n * a.tiles_x * a.tiles_y) return;
-    } else {
-        bx = blockIdx.x;
-        cblk = blockIdx.y;
-    }
-    const int tx_i = bx % a.tiles_x; bx /= a.tiles_x;
-    const int ty_i = bx % a.tiles_y;
-    const int n = bx / a.tiles_y;
-    const int oy0 = ty_i * TH, ox0 = tx_i * TW;
-    const int cobase = cblk * COT;
+    ConvTile tile; // (the grid is k_conv_s3's: channel blocks of one pixel tile consecutive on one XCD)
+    if (!conv_tile<TH, TW, COT>(a, tile)) return;
+    const int n = tile.n;
     const int hw = a.h * a.w_;
     const u32x4 *wsrc = (const u32x4 *)a.ws3;
     const int nchunks = a.cin >> 4;
@@ -80,27 +63,8 @@ void k_conv_s3p(ConvArgs a)
         bofs[pt] = hsel * PP + (m / TW) * PW + (m % TW);
     }
     const int aofs = hsel * COT + l31;
-    int pinfo[NPI];
-#pragma unroll
-    for (int j = 0; j < NPI; ++j) {
-        const int i = tid + j * NT;
-        int v = -1;
-        if (i < 2 * PP) {
-            const int cig = i / PP, r = i - cig * PP;
-            const int py = r / PW, px = r - py * PW;
-            const int gy = oy0 + py - PAD, gx = ox0 + px - PAD;
-            if (gy >= 0 && gy < a.h && gx >= 0 && gx < a.w_) v = cig * 8 * hw + gy * a.w_ + gx;
-        }
-        pinfo[j] = v;
-    }
-    int woff[NWU];
-#pragma unroll
-    for (int j = 0; j < NWU; ++j) {
-        const int u = tid + j * NT;
-        const int uu = u < WU ? u : WU - 1;
-        const int r = uu / COT, c = uu - r * COT;
-        woff[j] = r * a.cout + cobase + c;
-    }
+    int pinfo[NPI], woff[NWU]; // the staging plan: slomo_tile.h
+    s3_plan<KS, WP, PT, TW, COT, WU, false>(a, tile, pinfo, woff);
 
     // byte offsets of this thread's loads from a wave-uniform base: 32-bit, so that a load is `global_load ... v_off, s[base]`
     // with no per-load 64-bit vector address arithmetic (which costs the wave's issue slot ~20 clocks a load)
@@ -111,12 +75,7 @@ void k_conv_s3p(ConvArgs a)
     for (int j = 0; j < NWU; ++j) wbyte[j] = (uint32_t)woff[j] * 16u;
 
     f32x16 acc[CT][PT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int pt = 0; pt < PT; ++pt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ct][pt][r] = 0.f;
+    acc_zero(acc);
 
     float pv[2][NPI][8]; // two chunks of patch loads in flight
 #ifndef V2E_S3P_WD
@@ -128,11 +87,7 @@ void k_conv_s3p(ConvArgs a)
     // chunk index beyond the layer: clamped (the loads stay unconditional; what they fetch is staged into a buffer nobody reads)
     auto patch_base = [&](int chunk) -> const float * {
         const int cb = (chunk < nchunks ? chunk : nchunks - 1) << 4;
-        const float *src;
-        int cs, C;
-        if (cb < a.c0) { src = a.x0; cs = cb; C = a.c0; }
-        else { src = a.x1; cs = cb - a.c0; C = a.c1; }
-        return src + ((size_t)n * C + cs) * hw;
+        return concat_chunk(a, cb, n, hw);
     };
     auto load_item_half = [&](int set, int j, const float *base, int half) { // 4 of an item's 8 channels
         const int pi = pinfo[j];
@@ -225,19 +180,14 @@ void k_conv_s3p(ConvArgs a)
         auto micro = [&](auto M_tag) {
             constexpr int m = decltype(M_tag)::value;
             constexpr int t = m / 24, i = m % 24;
-            if constexpr (DBG == 1) return;
             if constexpr (t < 2 && i < 12) {
-                if constexpr (!(DBG & 32)) {
-                    constexpr int nb = (t + 1) & 1, c2 = i & 1;
-                    constexpr int piece_of[6] = {2, 0, 0, 2, 1, 1}; // A2 B0 A0 B2 A1 B1: what (2,0) (0,2) (1,1) need, in that order
-                    if constexpr ((i / 2) % 2 == 0) load_a1(t + 1, nb, piece_of[i / 2], c2);
-                    else load_b1(t + 1, nb, piece_of[i / 2], c2);
-                }
+                constexpr int nb = (t + 1) & 1, c2 = i & 1;
+                constexpr int piece_of[6] = {2, 0, 0, 2, 1, 1}; // A2 B0 A0 B2 A1 B1: what (2,0) (0,2) (1,1) need, in that order
+                if constexpr ((i / 2) % 2 == 0) load_a1(t + 1, nb, piece_of[i / 2], c2);
+                else load_b1(t + 1, nb, piece_of[i / 2], c2);
             } else if constexpr (t == 0) {
                 constexpr int e = (i - 12) / 3, st = (i - 12) % 3;
-                if constexpr (DBG & 16) {
-                    if constexpr (st == 0) { q[0][e] = __float_as_uint(pv[cp ^ 1][g][2 * e]); q[1][e] = __float_as_uint(pv[cp ^ 1][g][2 * e + 1]); q[2][e] = q[0][e]; }
-                } else if constexpr (st == 0) { // p0 = bf16(x)
+                if constexpr (st == 0) { // p0 = bf16(x)
                     const bool ok = pinfo[g] >= 0;
                     ra = ok ? pv[cp ^ 1][g][2 * e] : 0.f;
                     rb = ok ? pv[cp ^ 1][g][2 * e + 1] : 0.f;
@@ -255,25 +205,21 @@ void k_conv_s3p(ConvArgs a)
                     q[2][e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v2, bf16x2));
                 }
             } else if constexpr (t == 1 && i < 15) {
-                if constexpr (!(DBG & 8)) stage_item_piece(Pn, g, q, i - 12);
+                stage_item_piece(Pn, g, q, i - 12);
             } else if constexpr (t == 1 && i < 23) {
-                if constexpr (!(DBG & 4) && !(DBG & 64)) {
-                    const char *pb = (const char *)(pnext + (size_t)(i - 15) * hw); // uniform
-                    uint32_t off = pbyte[g];
-                    asm volatile("" : "+v"(off)); // keeps the zero-extension next to the load: `global_load v, v_off, s[base]`
-                    pv[cp ^ 1][g][i - 15] = *(const float *)(pb + off);
-                }
+                const char *pb = (const char *)(pnext + (size_t)(i - 15) * hw); // uniform
+                uint32_t off = pbyte[g];
+                asm volatile("" : "+v"(off)); // keeps the zero-extension next to the load: `global_load v, v_off, s[base]`
+                pv[cp ^ 1][g][i - 15] = *(const float *)(pb + off);
             } else if constexpr (t == 2 && i < 2 * NWU) {
                 constexpr int j = i / 2;
                 if constexpr (i % 2 == 0) {
                     const int u = tid + j * NT;
-                    if constexpr (!(DBG & 8)) { if (u < WU) Wn[u] = wv[ws][j]; }
+                    if (u < WU) Wn[u] = wv[ws][j];
                 } else {
-                    if constexpr (!(DBG & 4) && !(DBG & 128)) {
-                        uint32_t off = wbyte[j];
-                        asm volatile("" : "+v"(off));
-                        wv[ws][j] = *(const u32x4 *)((const char *)wnext + off);
-                    }
+                    uint32_t off = wbyte[j];
+                    asm volatile("" : "+v"(off));
+                    wv[ws][j] = *(const u32x4 *)((const char *)wnext + off);
                 }
             }
         };
@@ -281,7 +227,7 @@ void k_conv_s3p(ConvArgs a)
             constexpr int t = decltype(T_tag)::value;
             constexpr int cur = t & 1;
 #define S3P_MUL(PA, PB, CT_, PT_, M)                                                                                                    \
-    if constexpr (DBG != 2) acc[CT_][PT_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[cur][PA][CT_], bv[cur][PB][PT_], acc[CT_][PT_], 0, 0, 0); \
+    acc[CT_][PT_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[cur][PA][CT_], bv[cur][PB][PT_], acc[CT_][PT_], 0, 0, 0);                        \
     __builtin_amdgcn_sched_barrier(0);                                                                                                  \
     micro(std::integral_constant<int, t * 24 + (M)>{});                                                                                 \
     __builtin_amdgcn_sched_barrier(0);
@@ -306,31 +252,10 @@ void k_conv_s3p(ConvArgs a)
         step(std::integral_constant<int, 5>{}, pair);
     }
 
-    // epilogue as k_conv_s3: register r of a lane is channel (r&3)+8(r>>2)+4*hsel of pixel l31
-    uint32_t omax = 0u;
-#pragma unroll
-    for (int pt = 0; pt < PT; ++pt) {
-        const int m = (wave * PT + pt) * 32 + l31;
-        const int oy = oy0 + m / TW, ox = ox0 + (m % TW);
-        const bool pok = oy < a.h && ox < a.w_;
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ch = cobase + ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
-                if (pok) {
-                    float v = acc[ct][pt][r] + a.bias[ch];
-                    v = v > 0.f ? v : v * 0.1f;
-                    amax_fold(omax, v);
-                    a.y[(((size_t)n * a.cout + ch) * a.h + oy) * a.w_ + ox] = v;
-                }
-            }
-        }
-    }
-    if (a.am_out) amax_commit(a.am_out, omax);
+    conv_store<TW>(a, tile, acc, 1.0f);
 }
 
-template <int TW, int DBG = 0>
+template <int TW>
 static int launch_conv_s3p(const ConvArgs &a0, hipStream_t s)
 {
     ConvArgs a = a0;
@@ -338,19 +263,9 @@ static int launch_conv_s3p(const ConvArgs &a0, hipStream_t s)
     constexpr int PP = (TH + 2) * (TW + 2);
     constexpr size_t lds = (size_t)(2 * 6 * PP + 2 * 3 * 6 * 64) * 16;
     static_assert(lds <= 160 * 1024, "LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        V2E_HIP(hipFuncSetAttribute((const void *)k_conv_s3p<TW, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    a.tiles_x = (a.w_ + TW - 1) / TW;
-    a.tiles_y = (a.h + TH - 1) / TH;
     a.tl_on = g_s3p_timeline_on;
-    const int ntiles = a.n * a.tiles_x * a.tiles_y, ncb = a.cout / 64;
-    a.ncb = ncb >= 2 ? ncb : 0;
-    dim3 grid = a.ncb ? dim3((unsigned)((ntiles + 7) / 8 * 8 * ncb)) : dim3((unsigned)ntiles, (unsigned)ncb);
-    k_conv_s3p<TW, DBG><<<grid, 256, lds, s>>>(a);
-    return 0;
+    const int ncb = a.cout / 64;
+    return launch_tiles<k_conv_s3p<TW>>(a, TH, TW, ncb, ncb >= 2, 256, lds, s);
 }
 
 // 1 if the layer is not one of its shapes
