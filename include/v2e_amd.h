@@ -854,6 +854,30 @@ int v2e_stats_rows(const float *events, int64_t n, int H, int W, const int64_t *
 int v2e_stats_map_update(const float *events, const int64_t *sorted_keys, const int32_t *seg, int H, int W, float *last_t, int8_t *last_p,
                          void *stream);
 
+/* ------------------------------------------------------------- diagnostics */
+/* include/v2e_detmath.h evaluated on the device, an array at a time (v2e_amd/csrc/detmath_eval.hip): what tests/test_detmath_gpu.py
+ * compares with the CPU oracle's loops over the same header.  Nothing in the product path calls it.
+ * All arrays are device arrays of 32-bit words; a float travels as its bit pattern.  Element i of n (n <= 2^26):
+ *   fn                       a                                   b                                    out0 (out1)
+ *   V2E_DM_PHILOX, _KS       [n][4] counter                      [2] key                              [n][4] words
+ *   V2E_DM_LOGF, _EXPF       [n] x                               -                                    [n] f(x)
+ *   V2E_DM_SINCOS2PI         [n] u                               -                                    [n] sine ([n] cosine)
+ *   V2E_DM_NORMAL2           [n] word a                          [n] word b                           [n] cosine branch ([n] sine)
+ *   V2E_DM_SLEEF_SINHF       [n] x                               -                                    [n] sinh(x)
+ *   V2E_DM_PERM_APPLY, _INVERT [n] index < b[0]                  [6] n, seed low, high, clip, frame, iteration   [n] image
+ *   V2E_DM_NTH_SET_BIT_256   [n][8] mask, low word first         [n] r < popcount                     [n] position
+ *   V2E_DM_TS_FORMULA        [n][4] i, count, start, end         [n] step                             [n] timestamp
+ *   V2E_DM_DRAW_PAIR, _KS    [n] pixel                           [5] seed low, high, clip, pair, want_normal   [n][4] randn_odd, u_odd, randn_even, u_even
+ *   V2E_DM_DRAW_FRAME        [n] pixel                           [4] seed low, high, clip, frame      [n] leak normal ([n] shot uniform)
+ *   V2E_DM_DRAW_PNOISE       [n] pixel                           [4] seed low, high, clip, frame      [n] normal
+ *   V2E_DM_DRAW_INIT         [n] pixel                           [3] seed low, high, clip             [n][4] v2e_draw_init's n_pos, n_neg, n_rate, then v2e_draw_scidvs */
+enum {
+    V2E_DM_PHILOX = 0, V2E_DM_PHILOX_KS, V2E_DM_LOGF, V2E_DM_EXPF, V2E_DM_SINCOS2PI, V2E_DM_NORMAL2, V2E_DM_SLEEF_SINHF,
+    V2E_DM_PERM_APPLY, V2E_DM_PERM_INVERT, V2E_DM_NTH_SET_BIT_256, V2E_DM_TS_FORMULA, V2E_DM_DRAW_PAIR, V2E_DM_DRAW_PAIR_KS,
+    V2E_DM_DRAW_FRAME, V2E_DM_DRAW_PNOISE, V2E_DM_DRAW_INIT, V2E_DM_COUNT
+};
+int v2e_detmath_eval(int fn, const uint32_t *a, const uint32_t *b, uint32_t *out0, uint32_t *out1, int64_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,7 +95,8 @@ V2E_HD float v2e_u2f(uint32_t u) { union { float f; uint32_t u; } c; c.u = u; re
 
 /* ------------------------------------------------------- deterministic math */
 
-/* ln(x) for normal positive x.  ~1.5 ulp; deterministic. */
+/* ln(x) for normal positive x; deterministic.  Over all 2^24 values of v2e_u01_open0 the error against float64 is at most 2.508
+ * float32 spacings (at x = 13 088 785 * 2^-24) and 5.1e-7 absolute; ln(1) = +0 (tests/test_detmath.py, exhaustive). */
 V2E_HD float v2e_det_logf(float x)
 {
     uint32_t ux = v2e_f2u(x);

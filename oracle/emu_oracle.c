@@ -205,6 +205,92 @@ EXPORT float v2e_oracle_det_logf(float x) { return v2e_det_logf(x); }
 EXPORT float v2e_oracle_det_expf(float x) { return v2e_det_expf(x); }
 EXPORT float v2e_oracle_normal(uint32_t a, uint32_t b) { return v2e_normal(a, b); }
 
+/* ---- v2e_detmath.h an array at a time (tests/test_detmath.py, tests/test_detmath_gpu.py): each is a loop over the header's
+ * function and nothing else.  Floats go in and out as they are; pixels are pixel0 .. pixel0 + n - 1. */
+EXPORT void v2e_oracle_philox_words(const uint32_t *ctr /* [n][4] */, uint32_t k0, uint32_t k1, int key_schedule, int64_t n,
+                                    uint32_t *out /* [n][4] */)
+{
+    v2e_philox_keys ks;
+    v2e_philox_key_schedule(k0, k1, &ks);
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t *c = ctr + 4 * i;
+        if (key_schedule) v2e_philox4x32_ks(c[0], c[1], c[2], c[3], &ks, out + 4 * i);
+        else v2e_philox4x32(c[0], c[1], c[2], c[3], k0, k1, out + 4 * i);
+    }
+}
+
+EXPORT void v2e_oracle_det_logf_arr(const float *x, float *y, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) y[i] = v2e_det_logf(x[i]);
+}
+
+EXPORT void v2e_oracle_det_expf_arr(const float *x, float *y, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) y[i] = v2e_det_expf(x[i]);
+}
+
+EXPORT void v2e_oracle_sincos2pi_arr(const float *u, float *sn, float *cs, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) v2e_det_sincos2pi(u[i], sn + i, cs + i);
+}
+
+EXPORT void v2e_oracle_normal2_arr(const uint32_t *a, const uint32_t *b, float *n_cos, float *n_sin, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) v2e_normal2(a[i], b[i], n_cos + i, n_sin + i);
+}
+
+EXPORT void v2e_oracle_draw_pair(uint64_t seed, uint32_t clip, uint32_t pair, uint32_t pixel0, int64_t n, int want_normal,
+                                 int key_schedule, float *out /* [n][4]: randn_odd, u_odd, randn_even, u_even */)
+{
+    v2e_philox_keys ks;
+    v2e_philox_key_schedule((uint32_t)seed, (uint32_t)(seed >> 32), &ks);
+    for (int64_t i = 0; i < n; ++i) {
+        float *o = out + 4 * i;
+        if (key_schedule) v2e_draw_pair_ks(&ks, clip, pair, pixel0 + (uint32_t)i, want_normal, o, o + 1, o + 2, o + 3);
+        else v2e_draw_pair(seed, clip, pair, pixel0 + (uint32_t)i, want_normal, o, o + 1, o + 2, o + 3);
+    }
+}
+
+EXPORT void v2e_oracle_draw_frame(uint64_t seed, uint32_t clip, uint32_t frame, uint32_t pixel0, int64_t n, float *leak_randn,
+                                  float *shot_u)
+{
+    for (int64_t i = 0; i < n; ++i) v2e_draw_frame(seed, clip, frame, pixel0 + (uint32_t)i, leak_randn + i, shot_u + i);
+}
+
+EXPORT void v2e_oracle_draw_pnoise(uint64_t seed, uint32_t clip, uint32_t frame, uint32_t pixel0, int64_t n, float *out)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = v2e_draw_pnoise(seed, clip, frame, pixel0 + (uint32_t)i);
+}
+
+EXPORT void v2e_oracle_draw_init(uint64_t seed, uint32_t clip, uint32_t pixel0, int64_t n, float *n_pos, float *n_neg, float *n_rate)
+{
+    for (int64_t i = 0; i < n; ++i) v2e_draw_init(seed, clip, pixel0 + (uint32_t)i, n_pos + i, n_neg + i, n_rate + i);
+}
+
+EXPORT void v2e_oracle_draw_scidvs(uint64_t seed, uint32_t clip, uint32_t pixel0, int64_t n, float *out)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = v2e_draw_scidvs(seed, clip, pixel0 + (uint32_t)i);
+}
+
+EXPORT void v2e_oracle_perm_map(uint64_t seed, uint32_t clip, uint32_t frame, uint32_t iter, uint32_t n, int invert,
+                                const uint32_t *c, int64_t count, uint32_t *out)
+{
+    v2e_perm_t pm;
+    v2e_perm_init(&pm, seed, clip, frame, iter, n);
+    for (int64_t i = 0; i < count; ++i) out[i] = invert ? v2e_perm_invert(&pm, c[i]) : v2e_perm_apply(&pm, c[i]);
+}
+
+EXPORT void v2e_oracle_nth_set_bit_256_arr(const uint64_t *m /* [n][4] */, const uint32_t *r, int64_t n, uint32_t *out)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = v2e_nth_set_bit_256(m[4 * i], m[4 * i + 1], m[4 * i + 2], m[4 * i + 3], r[i]);
+}
+
+EXPORT void v2e_oracle_ts_formula_arr(const uint32_t *i_n /* [n][2]: i, count */, const float *start, const float *end,
+                                      const float *step, int64_t n, float *out)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = v2e_ts_formula(i_n[2 * i], i_n[2 * i + 1], start[i], end[i], step[i]);
+}
+
 /* ------------------------------------------------------------- first frame */
 /*
  * emulator.py:681-717 and _init :439-511.  frame: float64 [H*W].

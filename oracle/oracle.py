@@ -204,6 +204,114 @@ def ts_formula(t_prev, t_frame, n):
     return ts
 
 
+# ---- include/v2e_detmath.h an array at a time (tests/test_detmath.py, tests/test_detmath_gpu.py)
+def _u32(a):
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def _f32(a):
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def philox_words(ctr, k0, k1, key_schedule=False):
+    """v2e_philox4x32 (or v2e_philox4x32_ks) of the counters ctr[n][4] under the key (k0, k1): uint32 [n][4]"""
+    ctr = _u32(ctr).reshape(-1, 4)
+    out = np.empty_like(ctr)
+    lib().v2e_oracle_philox_words(_p(ctr), C.c_uint32(k0), C.c_uint32(k1), C.c_int(1 if key_schedule else 0),
+                                  C.c_int64(len(ctr)), _p(out))
+    return out
+
+
+def det_logf(x):
+    x = _f32(x)
+    y = np.empty_like(x)
+    lib().v2e_oracle_det_logf_arr(_p(x), _p(y), C.c_int64(x.size))
+    return y
+
+
+def det_expf(x):
+    x = _f32(x)
+    y = np.empty_like(x)
+    lib().v2e_oracle_det_expf_arr(_p(x), _p(y), C.c_int64(x.size))
+    return y
+
+
+def det_sincos2pi(u):
+    u = _f32(u)
+    s, c = np.empty_like(u), np.empty_like(u)
+    lib().v2e_oracle_sincos2pi_arr(_p(u), _p(s), _p(c), C.c_int64(u.size))
+    return s, c
+
+
+def normal2(a, b):
+    """(cosine branch, sine branch) of v2e_normal2 for the word pairs (a[i], b[i])"""
+    a, b = _u32(a), _u32(b)
+    assert a.shape == b.shape
+    nc, ns = np.empty(a.shape, np.float32), np.empty(a.shape, np.float32)
+    lib().v2e_oracle_normal2_arr(_p(a), _p(b), _p(nc), _p(ns), C.c_int64(a.size))
+    return nc, ns
+
+
+def draw_pair(seed, clip, pair, pixel0, n, want_normal=True, key_schedule=False):
+    """v2e_draw_pair (or v2e_draw_pair_ks) of pixels pixel0 .. pixel0 + n - 1: float32 [n][4] = randn_odd, u_odd, randn_even, u_even"""
+    out = np.empty((n, 4), np.float32)
+    lib().v2e_oracle_draw_pair(C.c_uint64(seed), C.c_uint32(clip), C.c_uint32(pair), C.c_uint32(pixel0), C.c_int64(n),
+                               C.c_int(1 if want_normal else 0), C.c_int(1 if key_schedule else 0), _p(out))
+    return out
+
+
+def draw_frame(seed, clip, frame, pixel0, n):
+    a, b = np.empty(n, np.float32), np.empty(n, np.float32)
+    lib().v2e_oracle_draw_frame(C.c_uint64(seed), C.c_uint32(clip), C.c_uint32(frame), C.c_uint32(pixel0), C.c_int64(n), _p(a), _p(b))
+    return a, b
+
+
+def draw_pnoise(seed, clip, frame, pixel0, n):
+    a = np.empty(n, np.float32)
+    lib().v2e_oracle_draw_pnoise(C.c_uint64(seed), C.c_uint32(clip), C.c_uint32(frame), C.c_uint32(pixel0), C.c_int64(n), _p(a))
+    return a
+
+
+def draw_init(seed, clip, pixel0, n):
+    a, b, c = np.empty(n, np.float32), np.empty(n, np.float32), np.empty(n, np.float32)
+    lib().v2e_oracle_draw_init(C.c_uint64(seed), C.c_uint32(clip), C.c_uint32(pixel0), C.c_int64(n), _p(a), _p(b), _p(c))
+    return a, b, c
+
+
+def draw_scidvs(seed, clip, pixel0, n):
+    a = np.empty(n, np.float32)
+    lib().v2e_oracle_draw_scidvs(C.c_uint64(seed), C.c_uint32(clip), C.c_uint32(pixel0), C.c_int64(n), _p(a))
+    return a
+
+
+def perm_map(seed, clip, frame, it, n, c, invert=False):
+    """v2e_perm_apply (or v2e_perm_invert) of the indices c under the bijection of (seed, clip, frame, it) on [0, n)"""
+    c = _u32(c)
+    out = np.empty_like(c)
+    lib().v2e_oracle_perm_map(C.c_uint64(seed), C.c_uint32(clip), C.c_uint32(frame), C.c_uint32(it), C.c_uint32(n),
+                              C.c_int(1 if invert else 0), _p(c), C.c_int64(c.size), _p(out))
+    return out
+
+
+def nth_set_bit_256_arr(masks, r):
+    """v2e_nth_set_bit_256 of the masks uint64 [n][4] and ranks r[n]"""
+    m = np.ascontiguousarray(masks, dtype=np.uint64).reshape(-1, 4)
+    r = _u32(r)
+    assert len(m) == r.size
+    out = np.empty(r.size, np.uint32)
+    lib().v2e_oracle_nth_set_bit_256_arr(_p(m), _p(r), C.c_int64(r.size), _p(out))
+    return out
+
+
+def ts_formula_arr(i, count, start, end, step):
+    """v2e_ts_formula(i, count, start, end, step) element by element"""
+    i_n = np.ascontiguousarray(np.stack([_u32(i), _u32(count)], axis=1))
+    start, end, step = _f32(start), _f32(end), _f32(step)
+    out = np.empty(len(i_n), np.float32)
+    lib().v2e_oracle_ts_formula_arr(_p(i_n), _p(start), _p(end), _p(step), C.c_int64(len(i_n)), _p(out))
+    return out
+
+
 # --------------------------------------------------------------- emulator
 class OracleEmulator:
     """CPU restatement of v2ecore.emulator.EventEmulator (hot path only)."""

@@ -11,7 +11,10 @@ def test_small_memset_nodes_in_a_replayed_graph():
     """hipMemsetAsync captured into a hipGraph wrote garbage into 16..160-byte buffers from the third
     replay of the same executable graph on ROCm 7.0 / HIP 7.0.5, which is why every zero-fill inside a captured run is a
     kernel node (k_zero_words).  This test replays such a graph: it passes when memset nodes behave (the workaround could
-    then go), and reports the known defect as an expected failure otherwise."""
+    then go), and reports the known defect as an expected failure otherwise.
+    The 0xAB fills go to the graph's own stream, ahead of each launch.  (They used to go to the default stream, behind which a
+    non-blocking stream does not order, and hipMemset on device memory returns before the fill has run: on a busy device the fill
+    landed after the graph's zeros and read as the defect -- profiles/r20_emulator_experiments.txt, item 6.)"""
     hip = C.CDLL("libamdhip64.so")
     vp = C.c_void_p
     hip.hipMalloc.argtypes = [C.POINTER(vp), C.c_size_t]
@@ -46,7 +49,7 @@ def test_small_memset_nodes_in_a_replayed_graph():
     bad = []
     for rep in range(6):
         for p, n in zip(bufs, sizes):
-            ok(hip.hipMemset(p, 0xAB, n))
+            ok(hip.hipMemsetAsync(p, 0xAB, n, s))
         ok(hip.hipGraphLaunch(ex, s))
         ok(hip.hipStreamSynchronize(s))
         for p, n in zip(bufs, sizes):

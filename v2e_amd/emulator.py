@@ -304,7 +304,9 @@ class EventEmulator(object):
         self._max_iters = max_iters
         if seed != 0:  # emulator.py:221-224
             torch.manual_seed(seed)
-            np.random.seed(seed)
+            # numpy takes 32 bits.  Philox mode keys its streams with all 64 bits of the seed (P.seed), so there a larger seed is
+            # valid and numpy gets its low word; tape mode raises ValueError like the reference
+            np.random.seed(seed if self.rng_mode == "tape" else seed & 0xFFFFFFFF)
             random.seed(seed)
 
         event_files.open_sinks(self, dvs_h5, dvs_aedat2, dvs_aedat4, dvs_text)
