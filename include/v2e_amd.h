@@ -824,6 +824,26 @@ int v2e_patches_features(const float *events, int64_t n, int H, int W, const int
 int v2e_patches_map_update(const float *events, const int64_t *sorted_keys, const int32_t *seg, int H, int W, float *last_t, int8_t *last_p,
                            void *stream);
 
+/* A learned patch filter in one pass: the patch of v2e_patches_features in mode 1 ("linear") gathered, a one-hidden-layer MLP
+ * evaluated on it and one float32 score per row written, with no feature in global memory (v2e_amd/csrc/mlpf.hip; host side
+ * v2e_amd/mlpf.py, MLPFilter).
+ * Rows, validity, carried maps and the per-row patch are exactly v2e_patches_features' with mode 1 and the same tau (finite, > 0).
+ * The input of row i is its patch flattened as [2][P][P], P = 2 * radius + 1: x[c * P * P + (dy + r) * P + (dx + r)], K = 2 * P * P
+ * entries (18, 50 or 98), all finite.
+ * Network: w1 float32 [hidden][K], b1 [hidden], w2 [hidden], b2 [1], device arrays, 1 <= hidden <= 64, all finite (the caller checks).
+ * Arithmetic: a_j = (double)b1[j]; for k = 0 .. K-1 ascending a_j = a_j + (double)w1[j][k] * (double)x[k] (the product of two
+ * float32 values is exact in float64, so each step is one float64 rounding, with or without an fma).  h_j = (float)a_j, rounded to
+ * nearest even; h_j = h_j > 0 ? h_j : 0, so a NaN becomes 0.  s = (double)b2; for j ascending s = s + (double)w2[j] * (double)h_j;
+ * scores[i] = (float)s.  No transcendental: the score is the logit.
+ * valid[i] (uint8) = 1 for a valid row; a bad row gets valid 0, the quiet NaN 0x7fc00000 as its score and mask 0.
+ * mask_or_null (uint8 [n]): mask[i] = valid[i] && (double)scores[i] >= threshold (threshold not NaN).
+ * Writes EVERY element of scores[n], valid[n] and mask[n]; the maps are only read.  One pass (n <= 2^31 - 1 rows, H * W <= 2^31 - 1)
+ * is v2e_denoise_keys, a sort of the keys, v2e_denoise_segments, this call, then v2e_patches_map_update on the same stream.
+ * events must be 16-byte aligned.  Bad arguments return V2E_EINVAL before anything is launched. */
+int v2e_patches_mlp_scores(const float *events, int64_t n, int H, int W, const int64_t *sorted_keys, const int32_t *seg, const float *last_t,
+                           const int8_t *last_p, int radius, double tau, const float *w1, const float *b1, int hidden, const float *w2,
+                           const float *b2, float *scores, uint8_t *valid, double threshold, uint8_t *mask_or_null, void *stream);
+
 /* A stream's own statistics: per-pixel counts, same-pixel inter-event intervals and time-bin counts of the rows of device-resident
  * runs (v2e_amd/csrc/stats.hip; host side v2e_amd/stats.py, EventStats).
  * Rows and validity: rows are events[n][4] = (t, x = column, y = row, p), taken in row order; a row is bad under exactly

@@ -205,6 +205,7 @@ SIGNATURES = {
     "v2e_denoise_map_update": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "v2e_patches_features": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp]),
     "v2e_patches_map_update": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "v2e_patches_mlp_scores": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _d, _vp, _vp, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp]),
     "v2e_stats_rows": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _i, _vp,
                             _i, _vp, _vp]),
     "v2e_stats_map_update": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

@@ -17,7 +17,8 @@
 // The lookup "the latest earlier row at q" is denoise.hip's: v2e_denoise_keys gives row i the key pixel << 32 | i, the host sorts
 // the keys, v2e_denoise_segments finds each pixel's stretch, and rowkeys.h's latest_before searches q's stretch for that row;
 // one 16-byte gather of it supplies both t and p.  Every entry is then independent of every other, so the result depends on
-// the row order alone, not on scheduling or on how a clip is cut into calls or passes.
+// the row order alone, not on scheduling or on how a clip is cut into calls or passes.  The rule of one entry is patch_entry.h's
+// patch_entry, which mlpf.hip's fused kernel calls as well.
 //
 // Mapping: one thread per (row, offset), the rows taken in sorted-key (pixel) order as in k_denoise_ages: the P * P lanes of a row
 // read adjacent seg entries, neighbouring rows search neighbouring stretches, and a row's lanes write two contiguous stretches of
@@ -26,66 +27,34 @@
 // slower at r = 3: 59 against 51 us on 137 k rows, 11.3 against 4.2 ms on 4.4 M rows, profiles/r17_event_patches.txt; only the
 // sorted order was kept.)
 #include "common.h"
-#include "rowkeys.h"
+#include "patch_entry.h"
 
 namespace {
 
 constexpr int FEATURES_MAX_BLOCKS = 1 << 16;
 
 struct PatchArgs {
-    const float4 *ev;
+    PatchSource src;             // rows, row index and carried maps
     int n;                       // rows of this pass
-    int H, W;
-    const long long *sorted;     // the sorted keys
-    const int *seg;              // [H*W + 1]
-    const float *last_t;         // [H*W], the carried maps (read only here)
-    const signed char *last_p;   // [H*W]
     int mode;                    // 0 age, 1 linear
     double tau;
     float *out;                  // [n][2][P][P]
     unsigned char *valid;        // [n]
 };
 
-__device__ __forceinline__ float pos_inf() { return __int_as_float(0x7f800000); }
-
 template <int R>
 __global__ __launch_bounds__(256) void k_patches_features(PatchArgs a)
 {
     constexpr int P = 2 * R + 1, PP = P * P;
-    const int W = a.W, H = a.H;
-    const long long total = (long long)valid_keys(a.seg, H, W, a.n) * PP;
+    const int W = a.src.W, H = a.src.H;
+    const long long total = (long long)valid_keys(a.src.seg, H, W, a.n) * PP;
     for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < total; g += (long long)gridDim.x * 256) {
         const int j = (int)(g / PP), o = (int)(g - (long long)j * PP);
-        const RowKey key = decode_key(a.sorted[j], W);
+        const RowKey key = decode_key(a.src.sorted[j], W);
         const unsigned int i = key.i;
         if (i >= (unsigned int)a.n || key.p >= (long long)H * W) continue; // (not a key of this pass: nothing is written for it)
-        const float t = a.ev[i].x;
-        const int dy = o / P - R, dx = o - (o / P) * P - R;
-        const int qx = key.x + dx, qy = key.y + dy;
-        float f0 = a.mode ? 0.0f : pos_inf(), f1 = 0.0f; // none
-        if (qx >= 0 && qx < W && qy >= 0 && qy < H) {
-            const long long q = key.p + (long long)dy * W + dx;
-            unsigned int before;
-            float tq, pq;
-            if (latest_before(a.sorted, a.seg, q, i, &before)) {
-                const float4 e = a.ev[before];
-                tq = e.x;
-                pq = e.w > 0.0f ? 1.0f : -1.0f;
-            } else {
-                tq = a.last_t[q];
-                pq = (float)a.last_p[q];
-            }
-            if (tq != -pos_inf()) {
-                const double age = (double)t - (double)tq;
-                if (a.mode == 0) {
-                    f0 = (float)age;
-                    f1 = pq;
-                } else if (age < a.tau) {
-                    f0 = age <= 0.0 ? 1.0f : (float)(1.0 - age / a.tau);
-                    f1 = pq;
-                }
-            }
-        }
+        float f0, f1;
+        patch_entry<R>(a.src, key, a.src.ev[i].x, o, a.mode, a.tau, &f0, &f1);
         float *o_row = a.out + (long long)i * (2 * PP); // (64-bit: n * 2 * PP passes 2^31)
         o_row[o] = f0;
         o_row[PP + o] = f1;
@@ -138,8 +107,9 @@ int v2e_patches_features(const float *events, int64_t n, int H, int W, const int
     if (n == 0) return 0;
     const int P = 2 * radius + 1, PP = P * P;
     PatchArgs a;
-    a.ev = (const float4 *)events; a.n = (int)n; a.H = H; a.W = W; a.sorted = (const long long *)sorted_keys; a.seg = seg;
-    a.last_t = last_t; a.last_p = (const signed char *)last_p; a.mode = mode; a.tau = tau; a.out = out; a.valid = valid;
+    a.src.ev = (const float4 *)events; a.src.sorted = (const long long *)sorted_keys; a.src.seg = seg; a.src.last_t = last_t;
+    a.src.last_p = (const signed char *)last_p; a.src.H = H; a.src.W = W;
+    a.n = (int)n; a.mode = mode; a.tau = tau; a.out = out; a.valid = valid;
     const int64_t want = (n * PP + 255) / 256;
     const int blocks = (int)(want < FEATURES_MAX_BLOCKS ? want : FEATURES_MAX_BLOCKS);
     hipStream_t s = (hipStream_t)stream;

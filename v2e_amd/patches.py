@@ -162,7 +162,7 @@ def score_roc(scores, labels, thresholds, valid=None):
     float64; a NaN score passes none), labels bool [n] (True = signal), thresholds ascending and finite [T], valid bool [n] or None
     (rows to leave out altogether).  Returns {"passed": int64 [2,T] (noise row first, signal second), "tpr", "fpr": float64 [T]
     (passed / the valid rows of that label; NaN where there are none), "n_signal", "n_noise": 0-dim int64}, on the scores' device.
-    Integer counting (torch.bucketize and bincount): exact."""
+    Integer counting (torch.bucketize and scatter_add_, in roc_counts): exact."""
     if not (torch.is_tensor(scores) and torch.is_tensor(labels)):
         raise TypeError("score_roc takes tensors")
     if scores.dim() != 1 or not scores.dtype.is_floating_point:
@@ -176,14 +176,23 @@ def score_roc(scores, labels, thresholds, valid=None):
     T = int(thr.shape[0])
     if T < 1 or not bool(torch.isfinite(thr).all()) or bool((torch.diff(thr) <= 0).any()):
         raise ValueError("score_roc: thresholds must be finite and strictly ascending, at least one")
-    s = scores.to(torch.float64)
-    b = torch.bucketize(s, thr.to(dev), right=True)            # the number of thresholds <= score: the row passes thresholds[:b]
-    b = torch.where(torch.isnan(s), torch.zeros_like(b), b)
-    cell = b + (T + 1) * labels.to(dev).to(torch.int64)
-    if valid is not None:
-        cell = cell[valid.to(dev)]
-    hist = torch.bincount(cell, minlength=2 * (T + 1)).reshape(2, T + 1)
-    passed = torch.flip(torch.cumsum(torch.flip(hist[:, 1:], [1]), 1), [1])   # passed[:, b] = rows whose count is above b
-    total = hist.sum(1)
+    passed, total = roc_counts(scores, labels.to(dev), thr.to(dev), None if valid is None else valid.to(dev))
     rate = passed.to(torch.float64) / total.to(torch.float64)[:, None]       # (0 / 0: NaN)
     return {"passed": passed, "tpr": rate[1], "fpr": rate[0], "n_signal": total[1], "n_noise": total[0]}
+
+
+def roc_counts(scores, labels, thr, valid=None):
+    """score_roc's counting on tensors of one device, arguments already checked (thr: float64 [T]): (passed int64 [2,T], the valid
+    rows of each label int64 [2]).  Integer scatter-adds into a histogram of fixed size: exact, and nothing waits for the device."""
+    T = int(thr.shape[0])
+    s = scores.to(torch.float64)
+    b = torch.bucketize(s, thr, right=True)                    # the number of thresholds <= score: the row passes thresholds[:b]
+    b = torch.where(torch.isnan(s), torch.zeros_like(b), b)
+    cell = b + (T + 1) * labels.to(torch.int64)
+    if valid is not None:
+        cell = torch.where(valid, cell, torch.full_like(cell, 2 * (T + 1)))  # (a cell of their own, dropped below)
+    hist = torch.zeros((2 * (T + 1) + 1,), dtype=torch.int64, device=s.device)
+    hist.scatter_add_(0, cell, torch.ones_like(cell))
+    hist = hist[:-1].reshape(2, T + 1)
+    passed = torch.flip(torch.cumsum(torch.flip(hist[:, 1:], [1]), 1), [1])   # passed[:, b] = rows whose count is above b
+    return passed, hist.sum(1)
