@@ -874,6 +874,37 @@ int v2e_stats_rows(const float *events, int64_t n, int H, int W, const int64_t *
 int v2e_stats_map_update(const float *events, const int64_t *sorted_keys, const int32_t *seg, int H, int W, float *last_t, int8_t *last_p,
                          void *stream);
 
+/* The fixed-window filter (FWF of the DND21 denoising benchmark) scored for every (L, sigma, k) in one pass over the rows of a
+ * device-resident run (v2e_amd/csrc/window.hip; host side v2e_amd/window.py, WindowSweep).
+ * Rows and validity: rows are events[n][4] = (t, x = column, y = row, p), taken in row order; neither p nor the value of t is used.
+ * A row is bad under exactly DenoiseSweep's rule: it is counted, never enters the window, enters no histogram and gets keep = 0.
+ * The stream: the valid rows of all passes, v_0, v_1, ...; the window of v_m is v_{m-1} (depth 1) ... v_{m-D}, D = min(m, lmax),
+ * lmax the longest length of the table.  For a sigma and k = 1 .. 4, d = the smallest depth j at which k of the rows at depth
+ * 1 .. j have |x - x'| + |y - y'| <= sigma (a row at the same pixel counts), lmax + 1 if the window holds fewer.  The row passes
+ * FWF(L, sigma, k) iff d <= L: with bin(d) = the number of lengths strictly below d (bin n_lengths: passes none),
+ * hist[k-1][s][label][bin(d)] += 1, hist a device uint64 [4][n_sigmas][2][n_lengths+1], label 1 = signal, 0 = noise.  After its
+ * depths are read the row enters the window whatever any filter says.  All sums are integer atomics: the result depends on the row
+ * order only, and a clip cut into passes gives the same sums.
+ * A row of the stream is the word x | y << 16; 0xffffffff is "no row yet" (H, W <= 65535 leave it free).  tail (device uint32
+ * [lmax]) carries the last lmax words from pass to pass, the latest last, and starts as lmax words 0xffffffff.
+ * One pass (1 <= n <= 2^30 rows) is three calls on one stream; no call waits for the device or learns the number of valid rows:
+ * v2e_window_compact: xy (uint32 [lmax + n]) = the tail, then the words of the pass's valid rows in order; idx (int32 [n]): the
+ * row of the pass behind each of those words; n_valid (int32 [1]) = their number; blk: scratch, int32 [(n + 255) / 256]; both
+ * counters (device uint64 [2], the call's and the sweep's): [0] += valid rows, [1] += bad rows; keep (uint8 [n] or null) gets 0 at
+ * bad rows.  events must be 16-byte aligned.
+ * v2e_window_depths: depths, histogram and, with keep != null, keep[i] = (d <= keep_length) for every valid row, d taken for
+ * keep_sigma (any value >= 0) and keep_k (1 .. 4), keep_length in 1 .. lmax; none of the three has to be a table entry.  lengths:
+ * device int32 [n_lengths], 1 <= n_lengths <= 64, strictly ascending, 1 <= L <= 1024, the last one lmax (the caller checks);
+ * sigmas: HOST int32 [n_sigmas], 1 <= n_sigmas <= 8, strictly ascending, 0 .. 65535.  Labels as for v2e_denoise_ages.
+ * v2e_window_tail: tail = the last lmax words of xy; behind v2e_window_depths on the same stream. */
+int v2e_window_compact(const float *events, int64_t n, int H, int W, const uint32_t *tail, int lmax, uint32_t *xy, int32_t *idx,
+                       int32_t *blk, int32_t *n_valid, uint64_t *call_counters, uint64_t *seen_counters, uint8_t *keep, void *stream);
+int v2e_window_depths(const uint32_t *xy, const int32_t *idx, int64_t n, const int32_t *n_valid, const int32_t *lengths, int n_lengths,
+                      int lmax, const int32_t *sigmas, int n_sigmas, const uint8_t *labels, const int64_t *label_bounds,
+                      int n_label_bounds, int64_t row0, uint64_t *hist, uint8_t *keep, int keep_length, int64_t keep_sigma, int keep_k,
+                      void *stream);
+int v2e_window_tail(const uint32_t *xy, const int32_t *n_valid, int64_t n, int lmax, uint32_t *tail, void *stream);
+
 /* ------------------------------------------------------------- diagnostics */
 /* include/v2e_detmath.h evaluated on the device, an array at a time (v2e_amd/csrc/detmath_eval.hip): what tests/test_detmath_gpu.py
  * compares with the CPU oracle's loops over the same header.  Nothing in the product path calls it.
