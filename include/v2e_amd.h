@@ -905,6 +905,30 @@ int v2e_window_depths(const uint32_t *xy, const int32_t *idx, int64_t n, const i
                       void *stream);
 int v2e_window_tail(const uint32_t *xy, const int32_t *n_valid, int64_t n, int lmax, uint32_t *tail, void *stream);
 
+/* The double-window filter (DWF of the same benchmark, jAER's DoubleWindowFilter) scored for every (L, sigma, k) of three tables
+ * (v2e_amd/csrc/dwindow.hip; host side v2e_amd/dwindow.py, DoubleWindowSweep).  Rows, validity and the packed words are the
+ * fixed-window filter's.  A setting owns two windows R and N of at most L rows each, empty at first; a valid row passes iff at
+ * least k rows of R and N together lie within L1 distance sigma of it (the same pixel counts); a passing row is appended to R, a
+ * failing one to N, and a window that now holds L + 1 rows drops its oldest.  Setting f = (ki * n_sigmas + si) * n_lengths + li.
+ * State between passes: rings (device uint32 [F][2][lmax], lmax the longest length: window R of setting f is a ring of L slots
+ * at rings[f][0][0 .. L), N at rings[f][1][0 .. L); 0xffffffff in a slot without a row and in every slot from L on: the start
+ * value of all of it), pos (device int32 [F][2], zero at first: the slot the window's next row goes to, which holds its oldest
+ * row once it is full) and passed (device uint64 [F][2]: passing noise rows, passing signal rows).
+ * One pass (1 <= n <= 2^30 rows) is three calls on one stream, none of which waits for the device:
+ * v2e_window_compact with lmax = 1 and a one-word tail: xy (uint32 [1 + n]), idx, n_valid as described there.
+ * v2e_dwindow_labels: lab (uint8 [n]) = the label of each of the pass's valid rows, in their order, from labels (a byte per row of
+ * the pass) or label_bounds (as for v2e_denoise_ages) or neither (all signal); totals (device uint64 [2]): [0] += valid noise
+ * rows, [1] += valid signal rows.
+ * v2e_dwindow_sweep: one wavefront per setting walks the pass's valid rows in order and updates rings, pos and passed; with
+ * keep != null, keep[i] = the verdict of the setting (lengths[keep_length], sigmas[keep_sigma], supports[keep_support]) -- the three
+ * are INDICES into the tables -- for every valid row i.  lengths, sigmas, supports: HOST int32 tables, strictly ascending, 1 to 64
+ * lengths in 1 .. 512, 1 to 8 sigmas in 0 .. 65535, 1 to 4 supports in 1 .. 4. */
+int v2e_dwindow_labels(const int32_t *idx, int64_t n, const int32_t *n_valid, const uint8_t *labels, const int64_t *label_bounds,
+                       int n_label_bounds, int64_t row0, uint8_t *lab, uint64_t *totals, void *stream);
+int v2e_dwindow_sweep(const uint32_t *xy, const int32_t *idx, const uint8_t *lab, int64_t n, const int32_t *n_valid, const int32_t *lengths,
+                      int n_lengths, const int32_t *sigmas, int n_sigmas, const int32_t *supports, int n_supports, uint32_t *rings,
+                      int32_t *pos, uint64_t *passed, uint8_t *keep, int keep_length, int keep_sigma, int keep_support, void *stream);
+
 /* ------------------------------------------------------------- diagnostics */
 /* include/v2e_detmath.h evaluated on the device, an array at a time (v2e_amd/csrc/detmath_eval.hip): what tests/test_detmath_gpu.py
  * compares with the CPU oracle's loops over the same header.  Nothing in the product path calls it.

@@ -14,6 +14,7 @@ from .tensors import EventTensorizer, plan_windows  # noqa: F401  (count / voxel
 from .sweep import ThresholdSweep, estimate_thresholds  # noqa: F401  (event counts for many thresholds in one pass over a clip)
 from .denoise import DenoiseResult, DenoiseSweep, denoise_rows  # noqa: F401  (correlation-filter ROC for all (k, tau) in one pass)
 from .window import WindowResult, WindowSweep  # noqa: F401  (fixed-window-filter ROC for all (L, sigma, k) in one pass)
+from .dwindow import DoubleWindowResult, DoubleWindowSweep  # noqa: F401  (double-window-filter ROC, one wavefront per (L, sigma, k))
 from .patches import EventPatches, frame_labels, score_roc  # noqa: F401  (per-event time-surface patches for learned denoisers)
 from .mlpf import MLPFilter  # noqa: F401  (a learned patch MLP scored per row in one fused pass)
 from .stats import EventStats, EventStatsResult  # noqa: F401  (a stream's rates, intervals and time-bin counts)
@@ -23,5 +24,5 @@ from ._capi import V2EAmdError  # noqa: F401
 __all__ = ["EventEmulator", "SuperSloMo", "EventRenderer", "ExposureMode", "Stage1", "V2EAmdError", "run_packets",
            "frame_times_text", "write_frame_times", "SyntheticToEvents", "moving_dot", "particles", "gradients", "barberpole",
            "EventTensorizer", "plan_windows", "ThresholdSweep", "estimate_thresholds", "DenoiseSweep", "DenoiseResult", "denoise_rows",
-           "WindowSweep", "WindowResult",
+           "WindowSweep", "WindowResult", "DoubleWindowSweep", "DoubleWindowResult",
            "EventPatches", "frame_labels", "score_roc", "MLPFilter", "EventStats", "EventStatsResult", "EventFileReader", "read_events"]

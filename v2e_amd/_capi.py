@@ -212,6 +212,9 @@ SIGNATURES = {
     "v2e_window_compact": (_i, [_vp, _i64, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "v2e_window_depths": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, _vp, _vp, _i, _i64, _vp, _vp, _i, _i64, _i, _vp]),
     "v2e_window_tail": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    "v2e_dwindow_labels": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    "v2e_dwindow_sweep": (_i, [_vp, _vp, _vp, _i64, _vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _i, _vp,
+                               _vp, _vp, _vp, _i, _i, _i, _vp]),
     "v2e_detmath_eval": (_i, [_i, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 

@@ -2,7 +2,7 @@
 the emulator's signal / noise labels for every (L, sigma, k) in one pass over the rows of device-resident runs, and hands out the
 keep-mask of one chosen (L, sigma, k).  The filter keeps no per-pixel map: it remembers the coordinates of the last L events and
 passes a new one when at least k of them lie within a spatial distance sigma.  The double-window filter of the same paper feeds its
-own verdicts back into its windows, which makes it serial per parameter setting: it is not built.
+own verdicts back into its windows, which makes it serial per parameter setting: `DoubleWindowSweep` (v2e_amd/dwindow.py) scores it.
 
 Rows are what every run hands out: device float32 [n,4] = (t, x = column, y = row, p), taken in row order; neither p nor the value
 of t is used.  A row is bad under exactly DenoiseSweep's rule (t not finite, or x / y not an integer value inside [0,W) / [0,H)):
@@ -44,34 +44,34 @@ MAX_SIDE = 65535
 XY_NONE = 0xFFFFFFFF  # the packed word of "no row yet"
 
 
-def _int_table(name, table, most, lo, hi):
+def _int_table(name, table, most, lo, hi, who="WindowSweep"):
     try:
         t = np.array(table, dtype=np.float64).reshape(-1)
     except (TypeError, ValueError):
-        raise ValueError("WindowSweep: %s must be a table of integers" % name) from None
+        raise ValueError("%s: %s must be a table of integers" % (who, name)) from None
     if not 1 <= len(t) <= most:
-        raise ValueError("WindowSweep: 1 to %d %s, got %d" % (most, name, len(t)))
+        raise ValueError("%s: 1 to %d %s, got %d" % (who, most, name, len(t)))
     if not np.all(np.isfinite(t)) or np.any(t != np.floor(t)) or np.any(t < lo) or np.any(t > hi) or np.any(np.diff(t) <= 0):
-        raise ValueError("WindowSweep: %s must be integers in %d .. %d, strictly ascending" % (name, lo, hi))
+        raise ValueError("%s: %s must be integers in %d .. %d, strictly ascending" % (who, name, lo, hi))
     return t.astype(np.int64)
 
 
-def _check_keep(keep, lmax):
+def _check_keep(keep, lmax, who="WindowSweep"):
     if keep is None:
         return None
     try:
         length, sigma, k = keep
         ints = (int(length), int(sigma), int(k))
     except (TypeError, ValueError, OverflowError):
-        raise ValueError("WindowSweep.add_run: keep must be (L, sigma, k), got %r" % (keep,)) from None
+        raise ValueError("%s.add_run: keep must be (L, sigma, k), got %r" % (who, keep,)) from None
     if ints != (length, sigma, k):
-        raise ValueError("WindowSweep.add_run: keep's L, sigma and k must be integers, got %r" % (keep,))
+        raise ValueError("%s.add_run: keep's L, sigma and k must be integers, got %r" % (who, keep,))
     if not 1 <= ints[0] <= lmax:
-        raise ValueError("WindowSweep.add_run: keep's L must be in 1 .. %d (the longest length), got %r" % (lmax, length))
+        raise ValueError("%s.add_run: keep's L must be in 1 .. %d (the longest length), got %r" % (who, lmax, length))
     if ints[1] < 0:
-        raise ValueError("WindowSweep.add_run: keep's sigma must be >= 0, got %r" % (sigma,))
+        raise ValueError("%s.add_run: keep's sigma must be >= 0, got %r" % (who, sigma,))
     if not 1 <= ints[2] <= MAX_SUPPORT:
-        raise ValueError("WindowSweep.add_run: keep's k must be in 1 .. %d, got %r" % (MAX_SUPPORT, k))
+        raise ValueError("%s.add_run: keep's k must be in 1 .. %d, got %r" % (who, MAX_SUPPORT, k))
     return ints
 
 
