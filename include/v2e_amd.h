@@ -375,10 +375,11 @@ int v2e_pack_conv_weight_s3(const float *w_oihw, void *w_s3, int cout, int cin, 
  * convolution divides it out again exactly.  Set v2e_conv_desc.split_kind = 2 | (scale_log2 << 8) with it. */
 int v2e_pack_conv_weight_h2(const float *w_oihw, void *w_h2, int cout, int cin, int k, int scale_log2, void *stream);
 /* Range guard of the two-float16-piece convolutions inside v2e_unet_forward: while a device flag is set here (per host thread;
- * NULL switches it off), a forward pass ORs 1 into it if a convolution's input holds an inf or a NaN (seen in the range slot its
- * producer left: the largest |output| of every convolution is tracked on the device, and a two-piece convolution stages its
- * activations times the power of two that puts that maximum in [2^13, 2^14) -- finite activations of any magnitude stay in
- * float16's normal range).  The caller zeroes the flag, runs the pass, reads it back, and on 1 redoes it with the exact three-piece
+ * NULL switches it off), a forward pass ORs 1 into it if the network input holds an inf or a NaN, or a convolution's output an inf
+ * (seen in the range slot the producer left: the largest |value| of the input and of every convolution's output is tracked on the
+ * device -- a NaN counts for the input only; one in a convolution's output needs an inf or a NaN upstream, which was flagged there
+ * -- and a two-piece convolution stages its activations times the power of two that puts that maximum in [2^13, 2^14): finite
+ * activations of any magnitude stay in float16's normal range).  The caller zeroes the flag, runs the pass, reads it back, and on 1 redoes it with the exact three-piece
  * weights -- what SloMoEngine's default conv math "auto" does.  A two-piece v2e_conv2d_lrelu called on its own stages unscaled and
  * is not watched. */
 int v2e_conv_set_range_flag(int *device_flag);
@@ -952,6 +953,17 @@ enum {
     V2E_DM_DRAW_FRAME, V2E_DM_DRAW_PNOISE, V2E_DM_DRAW_INIT, V2E_DM_COUNT
 };
 int v2e_detmath_eval(int fn, const uint32_t *a, const uint32_t *b, uint32_t *out0, uint32_t *out1, int64_t n, void *stream);
+
+/* The streaming passes a UNet forward runs between its convolutions, one at a time (v2e_amd/csrc/slomo_stream.h): what
+ * tests/test_slomo_stream_gpu.py compares with the CPU oracle bit for bit.  Nothing in the product path calls it.  Device arrays:
+ *   V2E_SS_AVGPOOL2, _UPSAMPLE2   x [nc][2h][2w] resp. [nc][h/2][w/2] (h, w even) -> float y [nc][h][w], through the launchers of
+ *                                 v2e_unet_forward: four outputs per thread when w is a multiple of 4, else one
+ *   ..._SCALAR                    the one-output-per-thread kernels at any width
+ *   V2E_SS_AMAX                   x [nc * h * w] -> uint32 y [1]: the range slot of the network input, RAISED to the bits of the
+ *                                 largest |x| (a NaN counts as 0x7fc00000); the caller preloads it
+ * V2E_EINVAL before anything is launched for a null pointer, a size that is not positive, an odd upsampling target or another op. */
+enum { V2E_SS_AVGPOOL2 = 0, V2E_SS_AVGPOOL2_SCALAR, V2E_SS_UPSAMPLE2, V2E_SS_UPSAMPLE2_SCALAR, V2E_SS_AMAX };
+int v2e_slomo_stream_eval(int op, const float *x, void *y, int64_t nc, int h, int w, void *stream);
 
 #ifdef __cplusplus
 }

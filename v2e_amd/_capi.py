@@ -216,11 +216,15 @@ SIGNATURES = {
     "v2e_dwindow_sweep": (_i, [_vp, _vp, _vp, _i64, _vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _i, _vp,
                                _vp, _vp, _vp, _i, _i, _i, _vp]),
     "v2e_detmath_eval": (_i, [_i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "v2e_slomo_stream_eval": (_i, [_i, _vp, _vp, _i64, _i, _i, _vp]),
 }
 
 # v2e_detmath_eval's functions (V2E_DM_* in include/v2e_amd.h, in the enum's order): diagnostics, called by the tests only
 DM_FUNCTIONS = ("PHILOX", "PHILOX_KS", "LOGF", "EXPF", "SINCOS2PI", "NORMAL2", "SLEEF_SINHF", "PERM_APPLY", "PERM_INVERT",
                 "NTH_SET_BIT_256", "TS_FORMULA", "DRAW_PAIR", "DRAW_PAIR_KS", "DRAW_FRAME", "DRAW_PNOISE", "DRAW_INIT")
+
+# v2e_slomo_stream_eval's passes (V2E_SS_* in include/v2e_amd.h, in the enum's order): diagnostics, called by the tests only
+SS_OPS = ("AVGPOOL2", "AVGPOOL2_SCALAR", "UPSAMPLE2", "UPSAMPLE2_SCALAR", "AMAX")
 
 # dev entry points the library exports outside include/v2e_amd.h: typed by lib() when present, never required
 DEV_SIGNATURES = {

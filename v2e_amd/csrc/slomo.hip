@@ -300,14 +300,16 @@ int v2e_unet_forward(const float *x, int cin, const v2e_conv_desc *cv, int cout,
 int v2e_slomo_prep(const float *i0, const float *i1, const float *flow, const float *tcoef, int n_t, int b, int h, int w,
                    float *x12, void *stream)
 {
-    V2E_REQUIRE(i0 && i1 && flow && tcoef && x12 && n_t > 0 && b > 0, "bad prep args");
+    V2E_REQUIRE(i0 && i1 && flow && tcoef && x12 && n_t > 0 && b > 0 && h > 0 && w > 0, "bad prep args");
+    V2E_REQUIRE((long long)n_t * b <= 65535, "too many samples for one prep launch");
     return launch_per_pixel(k_prep, n_t * b, h, w, (hipStream_t)stream, i0, i1, flow, tcoef, n_t, b, h, w, x12);
 }
 
 int v2e_slomo_fuse(const float *i0, const float *i1, const float *x12, const float *intrp, const float *tcoef, int n_t,
                    int b, int h, int w, float *out, void *stream)
 {
-    V2E_REQUIRE(i0 && i1 && x12 && intrp && tcoef && out && n_t > 0 && b > 0, "bad fuse args");
+    V2E_REQUIRE(i0 && i1 && x12 && intrp && tcoef && out && n_t > 0 && b > 0 && h > 0 && w > 0, "bad fuse args");
+    V2E_REQUIRE((long long)n_t * b <= 65535, "too many samples for one fuse launch");
     return launch_per_pixel(k_fuse, n_t * b, h, w, (hipStream_t)stream, i0, i1, x12, intrp, tcoef, n_t, b, h, w, out);
 }
 
@@ -337,6 +339,27 @@ int v2e_slomo_fuse_tab(const float *i0, const float *i1, const float *x12, const
 {
     V2E_REQUIRE(i0 && i1 && x12 && intrp && tcoef && tab && out && n > 0 && n <= 65535 && h > 0 && w > 0, "bad fuse_tab args");
     return launch_per_pixel(k_fuse_tab, n, h, w, (hipStream_t)stream, i0, i1, x12, intrp, tcoef, tab, h, w, out);
+}
+
+// diagnostics (include/v2e_amd.h): the streaming passes of a UNet forward on their own, through the launchers the pass uses
+int v2e_slomo_stream_eval(int op, const float *x, void *y, int64_t nc, int h, int w, void *stream)
+{
+    V2E_REQUIRE(x && y && nc > 0 && h > 0 && w > 0, "bad stream_eval args");
+    V2E_REQUIRE(op >= V2E_SS_AVGPOOL2 && op <= V2E_SS_AMAX, "unknown stream_eval op");
+    const bool up = op == V2E_SS_UPSAMPLE2 || op == V2E_SS_UPSAMPLE2_SCALAR;
+    V2E_REQUIRE(!up || (h % 2 == 0 && w % 2 == 0), "upsample target must be even");
+    V2E_REQUIRE(nc * h * w < ((int64_t)1 << 38), "stream_eval tensor too large");
+    hipStream_t s = (hipStream_t)stream;
+    const long long total = (long long)nc * h * w;
+    switch (op) {
+    case V2E_SS_AVGPOOL2: launch_avgpool2(x, (float *)y, nc, h, w, s); break;
+    case V2E_SS_AVGPOOL2_SCALAR: k_avgpool2_scalar<<<v2e_cdiv(total, 256), 256, 0, s>>>(x, (float *)y, nc, h, w); break;
+    case V2E_SS_UPSAMPLE2: launch_upsample2(x, (float *)y, nc, h, w, s); break;
+    case V2E_SS_UPSAMPLE2_SCALAR: k_upsample2_scalar<<<v2e_cdiv(total, 256), 256, 0, s>>>(x, (float *)y, nc, h, w); break;
+    default: launch_amax(x, total, (uint32_t *)y, s); break;
+    }
+    V2E_HIP(hipGetLastError());
+    return 0;
 }
 
 } // extern "C"

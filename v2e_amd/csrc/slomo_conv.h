@@ -57,7 +57,8 @@ struct LayerCtx {
 // |v| folded into a running maximum kept as float32 bits: one v_max_f32 with the |.| source modifier.  Non-negative floats and
 // +inf order like their bit patterns, so the per-wave / per-slot reductions are integer maxima.  A NaN is ignored by the
 // maximum: a NaN activation gives a NaN result in every conv math alike (as in the reference); what the range guard needs to
-// see is inf, and it does.
+// see in a convolution's output is inf, and it does.  (A NaN of the network input itself is recorded by k_amax's own fold,
+// slomo_stream.h.)
 __device__ __forceinline__ void amax_fold(uint32_t &m, float v)
 {
     m = __float_as_uint(fmaxf(__uint_as_float(m), fabsf(v)));

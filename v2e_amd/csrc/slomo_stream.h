@@ -335,7 +335,16 @@ __global__ __launch_bounds__(256) void k_fuse_tab(const float *__restrict__ i0, 
     fuse_sample(i0, i1, x12, intrp, coef + tab[3 * s + 1] * 6, tab[3 * s], s, h, w, p, out);
 }
 
-// largest |x| of a tensor into a range slot (the network input of v2e_unet_forward)
+// amax_fold for the network input, where a NaN must be seen too (fmaxf drops it): a NaN counts as the quiet-NaN pattern, which
+// orders above +inf as an unsigned word and has the all-ones exponent act_scale tests.  (The convolution epilogues keep amax_fold:
+// a NaN in a convolution's output needs an inf or a NaN upstream, and that one was flagged at the first layer.)
+__device__ __forceinline__ void amax_fold_nan(uint32_t &m, float v)
+{
+    const uint32_t b = v != v ? 0x7fc00000u : __float_as_uint(fabsf(v));
+    m = b > m ? b : m;
+}
+
+// largest |x| of a tensor into a range slot (the network input of v2e_unet_forward); the slot is only ever raised
 __global__ __launch_bounds__(256) void k_amax(const float *__restrict__ x, long long n, uint32_t *__restrict__ slot)
 {
     uint32_t m = 0u;
@@ -343,9 +352,9 @@ __global__ __launch_bounds__(256) void k_amax(const float *__restrict__ x, long 
     const float4 *x4 = (const float4 *)x;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
         const float4 v = x4[i];
-        amax_fold(m, v.x); amax_fold(m, v.y); amax_fold(m, v.z); amax_fold(m, v.w);
+        amax_fold_nan(m, v.x); amax_fold_nan(m, v.y); amax_fold_nan(m, v.z); amax_fold_nan(m, v.w);
     }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) amax_fold(m, x[(n4 << 2) + threadIdx.x]);
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) amax_fold_nan(m, x[(n4 << 2) + threadIdx.x]);
     amax_commit(slot, m);
 }
 
