@@ -25,6 +25,11 @@ void v2e_set_error(const char *fmt, ...);
         }                                                            \
     } while (0)
 
+// the label arguments of a labelled entry point: a byte per row, or a table of at least one bound, or neither
+#define V2E_REQUIRE_LABELS(labels, label_bounds, n_label_bounds) \
+    V2E_REQUIRE(!((labels) && (label_bounds)) && (!(label_bounds) || (n_label_bounds) >= 1), \
+                "labels: a byte per row or a table of bounds, not both")
+
 static inline int v2e_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // csdvs.hip: one frame's surround (diffuser) update enqueued on `s` without a host step (emu.hip's per-frame run loop)

@@ -122,12 +122,7 @@ __global__ __launch_bounds__(256) void k_denoise_ages(AgesArgs r)
         cswap(a[1], a[4]); cswap(a[3], a[6]);
         cswap(a[1], a[2]); cswap(a[3], a[4]); cswap(a[5], a[6]);
 
-        int label = 1;
-        if (r.labels) {
-            label = r.labels[i] ? 1 : 0;
-        } else if (lb) {
-            label = count_le<long long>(lb, r.n_lbounds, r.row0 + (long long)i) & 1;
-        }
+        const int label = row_label(r.labels, lb, r.n_lbounds, r.row0, i);
         int b = 0; // the bins ascend with k: each search starts at the bin before
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -187,7 +182,7 @@ int v2e_denoise_ages(const float *events, int64_t n, int H, int W, const int64_t
     V2E_REQUIRE(n >= 0 && n <= 0x7fffffff && H > 0 && W > 0 && (int64_t)H * W <= 0x7fffffff && ((events && sorted_keys) || n == 0) && seg &&
                 last_t && taus && hist && row0 >= 0, "bad args");
     V2E_REQUIRE(n_taus >= 1 && n_taus <= MAX_TAUS, "1 to 256 taus");
-    V2E_REQUIRE(!(labels && label_bounds) && (!label_bounds || n_label_bounds >= 1), "labels: a byte per row or a table of bounds, not both");
+    V2E_REQUIRE_LABELS(labels, label_bounds, n_label_bounds);
     V2E_REQUIRE(!keep || (keep_k >= 1 && keep_k <= 8 && keep_tau >= 0.0), "keep: k in 1 .. 8 and tau >= 0");
     V2E_REQUIRE(((uintptr_t)events & 15u) == 0, "rows must be 16-byte aligned");
     if (n == 0) return 0;

@@ -22,7 +22,7 @@
 // needs no counter of its own: the empty slots are pos .. L - 1 while any slot is empty.
 #include "common.h"
 #include "block_ops.h"
-#include "table_search.h"
+#include "rowkeys.h"
 
 namespace {
 
@@ -43,8 +43,7 @@ __global__ __launch_bounds__(256) void k_dwindow_labels(const int *__restrict__ 
     int label = 1;
     if (active) {
         const int i = idx[r];
-        if (labels) label = labels[i] ? 1 : 0;
-        else if (lbounds) label = count_le<long long>(lbounds, n_lbounds, row0 + (long long)i) & 1;
+        label = row_label(labels, lbounds, n_lbounds, row0, i);
         lab[r] = (unsigned char)label;
     }
     const int c1 = block_count(active && label == 1, s, 4);
@@ -187,7 +186,7 @@ int v2e_dwindow_labels(const int32_t *idx, int64_t n, const int32_t *n_valid, co
                        int n_label_bounds, int64_t row0, uint8_t *lab, uint64_t *totals, void *stream)
 {
     V2E_REQUIRE(n >= 1 && n <= (1 << 30) && idx && n_valid && lab && totals && row0 >= 0, "bad args");
-    V2E_REQUIRE(!(labels && label_bounds) && (!label_bounds || n_label_bounds >= 1), "labels: a byte per row or a table of bounds, not both");
+    V2E_REQUIRE_LABELS(labels, label_bounds, n_label_bounds);
     V2E_REQUIRE(((uintptr_t)totals & 7u) == 0 && ((uintptr_t)idx & 3u) == 0 && ((uintptr_t)n_valid & 3u) == 0, "counters and indices must be aligned");
     k_dwindow_labels<<<v2e_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(idx, (int)n, n_valid, labels, (const long long *)label_bounds,
                                                                          label_bounds ? n_label_bounds : 0, row0, lab,

@@ -1,6 +1,7 @@
 // rowkeys.h -- the row index of denoise.hip and patches.hip: which rows are valid, the sort key pixel << 32 | row of a valid row,
 // and "the latest earlier row at pixel q" in the sorted keys.  seg[p] (k_denoise_segments) is the number of sorted keys below
-// p << 32: pixel p's rows are sorted[seg[p] .. seg[p+1]), in row order, and seg[H*W] is the number of valid rows.
+// p << 32: pixel p's rows are sorted[seg[p] .. seg[p+1]), in row order, and seg[H*W] is the number of valid rows.  It also holds
+// the label rule of every kernel that takes the rows' signal / noise labels (row_label), window.hip's and dwindow.hip's included.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +24,17 @@ __device__ __forceinline__ long long row_pixel(const float4 e, int H, int W)
     const int x = pixel_coord(e.y, W), y = pixel_coord(e.z, H);
     if (x < 0 || y < 0 || !(fabsf(e.x) <= 3.402823466e+38f)) return -1;
     return (long long)y * W + x;
+}
+
+// The label of row i of a pass, 1 = signal, 0 = noise: labels[i] != 0 (a byte per row of the pass), else whether an odd number of
+// lbounds entries (ascending row indices of the whole call, in which the pass's row 0 is row0) is <= row0 + i, else signal.
+__device__ __forceinline__ int row_label(const unsigned char *labels, const long long *lbounds, int n_lbounds, long long row0,
+                                         long long i)
+{
+    int label = 1;
+    if (labels) label = labels[i] ? 1 : 0;
+    else if (lbounds) label = count_le<long long>(lbounds, n_lbounds, row0 + i) & 1;
+    return label;
 }
 
 struct RowKey { unsigned int i; long long p; int x, y; }; // row index, pixel = y * W + x (p < H * W <= 2^31 - 1)

@@ -103,8 +103,7 @@ __global__ __launch_bounds__(256) void k_stats_rows(StatsArgs a)
         int label = 1;
         if (active) {
             e = a.ev[key.i];
-            if (a.labels) label = a.labels[key.i] ? 1 : 0;
-            else if (a.lbounds) label = count_le<long long>(a.lbounds, a.n_lbounds, a.row0 + (long long)key.i) & 1;
+            label = row_label(a.labels, a.lbounds, a.n_lbounds, a.row0, key.i);
         }
         const int on = e.w > 0.0f ? 1 : 0, c = 2 * label + on;
 
@@ -213,7 +212,7 @@ int v2e_stats_rows(const float *events, int64_t n, int H, int W, const int64_t *
     V2E_REQUIRE(time_bounds ? (n_bins >= 1 && n_bins <= (1 << 20) && time_hist) : n_bins == 0, "time bounds: 1 to 2^20 bins, or none");
     V2E_REQUIRE(isi_replicas >= 1 && time_replicas >= 1 && isi_replicas <= ROWS_MAX_BLOCKS && time_replicas <= ROWS_MAX_BLOCKS,
                 "1 to 2048 replicas of each histogram");
-    V2E_REQUIRE(!(labels && label_bounds) && (!label_bounds || n_label_bounds >= 1), "labels: a byte per row or a table of bounds, not both");
+    V2E_REQUIRE_LABELS(labels, label_bounds, n_label_bounds);
     V2E_REQUIRE(((uintptr_t)events & 15u) == 0, "rows must be 16-byte aligned");
     if (n == 0) return 0;
     StatsArgs a;

@@ -168,12 +168,7 @@ template <int NS> __global__ __launch_bounds__(256) void k_window_depths(DepthAr
         }
         if (!active) continue;
         const int i = r.idx[row];
-        int label = 1;
-        if (r.labels) {
-            label = r.labels[i] ? 1 : 0;
-        } else if (r.lbounds) {
-            label = count_le<long long>(r.lbounds, r.n_lbounds, r.row0 + (long long)i) & 1;
-        }
+        const int label = row_label(r.labels, r.lbounds, r.n_lbounds, r.row0, i);
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             if (s >= S) continue;
@@ -241,7 +236,7 @@ int v2e_window_depths(const uint32_t *xy, const int32_t *idx, int64_t n, const i
     V2E_REQUIRE(n >= 1 && n <= (1 << 30) && xy && idx && n_valid && lengths && sigmas && hist && row0 >= 0, "bad args");
     V2E_REQUIRE(n_lengths >= 1 && n_lengths <= MAX_LENGTHS && lmax >= 1 && lmax <= MAX_LENGTH, "1 to 64 lengths, the longest 1 to 1024");
     V2E_REQUIRE(n_sigmas >= 1 && n_sigmas <= MAX_SIGMAS, "1 to 8 sigmas");
-    V2E_REQUIRE(!(labels && label_bounds) && (!label_bounds || n_label_bounds >= 1), "labels: a byte per row or a table of bounds, not both");
+    V2E_REQUIRE_LABELS(labels, label_bounds, n_label_bounds);
     V2E_REQUIRE(!keep || (keep_length >= 1 && keep_length <= lmax && keep_sigma >= 0 && keep_k >= 1 && keep_k <= MAX_SUPPORT),
                 "keep: L in 1 .. the longest length, sigma >= 0, k in 1 .. 4");
     DepthArgs r;

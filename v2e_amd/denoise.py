@@ -24,7 +24,6 @@ Scratch per row of a pass: 8 bytes of keys, 16 of the sort's output (sorted keys
 24 of the sort's own buffers: 48 bytes at the peak (measured, profiles/r15_denoise_sweep.txt), 1.5 GiB at the default 2^25 rows per
 pass; 1 byte more per row of the call with a keep mask or bool labels.
 """
-import ctypes as C
 import math
 
 import numpy as np
@@ -32,7 +31,8 @@ import torch
 
 from . import _capi, _rowpasses
 from ._capi import check, ptr, stream_ptr
-from ._rowpasses import DEFAULT_ROWS_PER_PASS
+from ._roc import RocResult
+from ._rowpasses import DEFAULT_ROWS_PER_PASS, label_bounds  # noqa: F401  (label_bounds: imported from here by users)
 
 MAX_TAUS = 256
 NEIGHBOURS = 8
@@ -62,24 +62,7 @@ def _check_keep(keep):
     return k_int, tau
 
 
-def label_bounds(counts, n_signal):
-    """The frame table of `add_run(counts=, n_signal=)` as one ascending int64 table of row indices, [2F]: frame f's signal rows
-    start at entry 2f (the sum of the counts before it), its noise rows at entry 2f + 1 (n_signal[f] rows later).  A row is a signal
-    row iff an odd number of entries is <= its index.  Returns (table, rows the counts cover)."""
-    c = np.asarray(counts, dtype=np.int64).reshape(-1)
-    s = np.asarray(n_signal, dtype=np.int64).reshape(-1)
-    if len(s) != len(c):
-        raise ValueError("DenoiseSweep.add_run: n_signal has %d entries, counts %d" % (len(s), len(c)))
-    if np.any(c < 0) or np.any(s < 0) or np.any(s > c):
-        raise ValueError("DenoiseSweep.add_run: need 0 <= n_signal[f] <= counts[f] in every frame")
-    off = np.concatenate([[0], np.cumsum(c)])
-    b = np.empty(2 * len(c), dtype=np.int64)
-    b[0::2] = off[:-1]
-    b[1::2] = off[:-1] + s
-    return b, int(off[-1])
-
-
-class DenoiseResult(object):
+class DenoiseResult(RocResult):
     """The histogram of a `DenoiseSweep` on the host, and the ROC it holds.
 
     hist      int64 [8,2,T+1]: hist[k-1, label, b] rows whose k-th smallest age falls in bin b (label 1 = signal, 0 = noise)
@@ -103,28 +86,11 @@ class DenoiseResult(object):
     def passed(self):
         return np.cumsum(self.hist[:, :, :-1], axis=2)
 
-    def _rate(self, label, n):
-        p = self.passed[:, label, :].astype(np.float64)
-        return p / n if n > 0 else np.full(p.shape, np.nan)
-
-    @property
-    def tpr(self):
-        return self._rate(1, self.n_signal)
-
-    @property
-    def fpr(self):
-        return self._rate(0, self.n_noise)
-
     def best(self):
         """(k, tau, tpr, fpr) at the first maximum of tpr - fpr, taken in (k ascending, tau ascending) order.  ValueError when there
         is no signal or no noise row (tpr - fpr is NaN everywhere)."""
-        tpr, fpr = self.tpr, self.fpr
-        d = (tpr - fpr).reshape(-1)
-        if np.all(np.isnan(d)):
-            raise ValueError("DenoiseResult.best: needs at least one signal and one noise row")
-        j = int(np.nanargmax(d))  # (the first maximum in C order)
-        k, b = divmod(j, len(self.taus))
-        return k + 1, float(self.taus[b]), float(tpr[k, b]), float(fpr[k, b])
+        (k, b), tpr, fpr = self._best("DenoiseResult")
+        return int(k) + 1, float(self.taus[b]), tpr, fpr
 
 
 class DenoiseSweep(object):
@@ -153,11 +119,6 @@ class DenoiseSweep(object):
             }
         return self._state
 
-    def _upload(self, a):
-        """A small host table to the device without waiting for it: through pinned memory of torch's caching host allocator, which
-        keeps the block until the copy has run."""
-        return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(self.device, non_blocking=True)
-
     def reset(self):
         """The map back to -inf, the histogram and n_bad to zero (enqueued on the current stream)."""
         if self._state is not None:
@@ -182,46 +143,22 @@ class DenoiseSweep(object):
         one waits for the device; the call does not), mask a device tensor in the rows' order."""
         # every ValueError before the library or the device is touched
         keep = _check_keep(keep)
-        if labels is not None and n_signal is not None:
-            raise ValueError("DenoiseSweep.add_run: labels or n_signal, not both")
-        if n_signal is not None and counts is None:
-            raise ValueError("DenoiseSweep.add_run: n_signal needs the run's counts")
-        bounds = covered = None
-        if n_signal is not None:
-            bounds, covered = label_bounds(counts, n_signal)
-        if rows is not None:
-            if not torch.is_tensor(rows):
-                raise TypeError("DenoiseSweep.add_run takes the run's rows as a device tensor")
-            if rows.dim() != 2 or rows.shape[1] != 4 or rows.dtype != torch.float32:
-                raise ValueError("DenoiseSweep.add_run: rows must be float32 [n,4]")
-        n = 0 if rows is None else int(rows.shape[0])
-        if labels is not None:
-            if not torch.is_tensor(labels):
-                labels = torch.from_numpy(np.ascontiguousarray(np.asarray(labels)))
-            if labels.dtype != torch.bool or labels.dim() != 1 or int(labels.shape[0]) != n:
-                raise ValueError("DenoiseSweep.add_run: labels must be bool [%d]" % n)
-        if covered is not None and covered != n:
-            raise ValueError("DenoiseSweep.add_run: counts sum to %d rows, the run has %d" % (covered, n))
-        if rows is not None and not rows.is_cuda:
-            raise TypeError("DenoiseSweep.add_run takes the run's rows as a device tensor")
+        n, labels, bounds = _rowpasses.check_run("DenoiseSweep", rows, counts, n_signal, labels, host_error=TypeError)
         st = self._dev()
         dev = self.device
         if n == 0:
-            zero, zero_bad = _rowpasses.no_rows(dev)
-            return {"n": zero, "n_bad": zero_bad, "mask": None if keep is None else torch.zeros((0,), dtype=torch.bool, device=dev)}
+            return _rowpasses.no_rows(dev, mask=True, keep=keep)
         rows = rows.to(dev).contiguous()
         lib = _capi.lib()
         stream = stream_ptr(dev)
         H, W, T = self.height, self.width, len(self.taus)
-        lab = None if labels is None else labels.to(dev, non_blocking=True).to(torch.uint8).contiguous()
-        lb = None if bounds is None else self._upload(bounds)
-        mask = None if keep is None else torch.empty((n,), dtype=torch.uint8, device=dev)
+        lab, lb = _rowpasses.labels_to_device(labels, bounds, dev)
+        mask = _rowpasses.new_mask(keep, n, dev)
         k, tau = keep if keep is not None else (1, 0.0)
         run = _rowpasses.RowPasses(self, rows, st["seg"], keep=mask)
         for r0, m, ev, skeys in run:
             check(lib.v2e_denoise_ages(ptr(ev), m, H, W, ptr(skeys), ptr(st["seg"]), ptr(st["last_t"]), ptr(st["taus"]), T,
-                                       None if lab is None else C.c_void_p(lab.data_ptr() + r0), ptr(lb),
-                                       0 if lb is None else int(lb.shape[0]), r0, ptr(st["hist"]), run.keep_ptr(r0), k, tau, stream),
+                                       *_rowpasses.label_args(lab, lb, r0), ptr(st["hist"]), run.keep_ptr(r0), k, tau, stream),
                   "v2e_denoise_ages")
             check(lib.v2e_denoise_map_update(ptr(ev), ptr(skeys), ptr(st["seg"]), H, W, ptr(st["last_t"]), stream),
                   "v2e_denoise_map_update")

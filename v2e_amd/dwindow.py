@@ -36,15 +36,15 @@ import torch
 
 from . import _capi, _rowpasses
 from ._capi import check, ptr, stream_ptr
-from .denoise import label_bounds
-from .window import MAX_LENGTHS, MAX_SIDE, MAX_SIGMA, MAX_SIGMAS, MAX_SUPPORT, XY_NONE, _check_keep, _int_table
+from ._roc import RocResult
+from .window import MAX_LENGTHS, MAX_SIDE, MAX_SIGMA, MAX_SIGMAS, MAX_SUPPORT, XY_NONE, check_keep, int_table
 
 MAX_LENGTH = 512
 DEFAULT_ROWS_PER_PASS = 1 << 18
 WHO = "DoubleWindowSweep"
 
 
-class DoubleWindowResult(object):
+class DoubleWindowResult(RocResult):
     """The counts of a `DoubleWindowSweep` on the host, and the ROC they hold.
 
     passed    int64 [NK,S,NL,2]: passed[ki, s, li, label] valid rows that pass DWF(lengths[li], sigmas[s], supports[ki])
@@ -56,6 +56,8 @@ class DoubleWindowResult(object):
     tpr, fpr  float64 [NK,S,NL]: passed signal rows / n_signal, passed noise rows / n_noise; NaN where the denominator is 0
     """
 
+    LABEL_AXIS = -1
+
     def __init__(self, passed, lengths, sigmas, supports, n_signal, n_noise, n_bad=0):
         self.lengths = np.array(lengths, dtype=np.int64).reshape(-1)
         self.sigmas = np.array(sigmas, dtype=np.int64).reshape(-1)
@@ -66,28 +68,11 @@ class DoubleWindowResult(object):
             raise ValueError("DoubleWindowResult: passed must be [%d, %d, %d, 2], got %r" % (shape[:3] + (self.passed.shape,)))
         self.n_signal, self.n_noise, self.n_bad = int(n_signal), int(n_noise), int(n_bad)
 
-    def _rate(self, label, n):
-        p = self.passed[:, :, :, label].astype(np.float64)
-        return p / n if n > 0 else np.full(p.shape, np.nan)
-
-    @property
-    def tpr(self):
-        return self._rate(1, self.n_signal)
-
-    @property
-    def fpr(self):
-        return self._rate(0, self.n_noise)
-
     def best(self):
         """(L, sigma, k, tpr, fpr) at the first maximum of tpr - fpr, taken in (k ascending, sigma ascending, L ascending) order.
         ValueError when there is no signal or no noise row (tpr - fpr is NaN everywhere)."""
-        tpr, fpr = self.tpr, self.fpr
-        d = (tpr - fpr).reshape(-1)
-        if np.all(np.isnan(d)):
-            raise ValueError("DoubleWindowResult.best: needs at least one signal and one noise row")
-        j = int(np.nanargmax(d))  # (the first maximum in C order)
-        ki, s, li = np.unravel_index(j, tpr.shape)
-        return int(self.lengths[li]), int(self.sigmas[s]), int(self.supports[ki]), float(tpr[ki, s, li]), float(fpr[ki, s, li])
+        (ki, s, li), tpr, fpr = self._best("DoubleWindowResult")
+        return int(self.lengths[li]), int(self.sigmas[s]), int(self.supports[ki]), tpr, fpr
 
 
 class DoubleWindowSweep(object):
@@ -98,9 +83,9 @@ class DoubleWindowSweep(object):
         self.height, self.width = int(height), int(width)
         if not (1 <= self.height <= MAX_SIDE and 1 <= self.width <= MAX_SIDE):  # (no per-pixel map: no limit on height * width)
             raise ValueError("%s: height and width must be in 1 .. %d" % (WHO, MAX_SIDE))
-        self.lengths = _int_table("lengths", lengths, MAX_LENGTHS, 1, MAX_LENGTH, WHO)
-        self.sigmas = _int_table("sigmas", sigmas, MAX_SIGMAS, 0, MAX_SIGMA, WHO)
-        self.supports = _int_table("supports", supports, MAX_SUPPORT, 1, MAX_SUPPORT, WHO)
+        self.lengths = int_table(WHO, "lengths", lengths, MAX_LENGTHS, 1, MAX_LENGTH)
+        self.sigmas = int_table(WHO, "sigmas", sigmas, MAX_SIGMAS, 0, MAX_SIGMA)
+        self.supports = int_table(WHO, "supports", supports, MAX_SUPPORT, 1, MAX_SUPPORT)
         self.max_length = int(self.lengths[-1])
         self.max_rows_per_pass = _rowpasses.check_rows_per_pass(WHO, max_rows_per_pass)
         self.device = torch.device(device)
@@ -170,66 +155,31 @@ class DoubleWindowSweep(object):
         Returns {"n": valid rows, "n_bad": bad rows, "mask": bool [n] or None}: n and n_bad are 0-dim int64 device tensors (reading
         one waits for the device; the call does not), mask a device tensor in the rows' order."""
         # every ValueError before the library or the device is touched
-        keep = _check_keep(keep, self.max_length, WHO)
+        keep = check_keep(WHO, keep, self.max_length)
         keep_at = None if keep is None else self._keep_indices(keep)
-        if labels is not None and n_signal is not None:
-            raise ValueError("%s.add_run: labels or n_signal, not both" % WHO)
-        if n_signal is not None and counts is None:
-            raise ValueError("%s.add_run: n_signal needs the run's counts" % WHO)
-        bounds = covered = None
-        if n_signal is not None:
-            bounds, covered = label_bounds(counts, n_signal)
-        if rows is not None:
-            if not torch.is_tensor(rows):
-                raise TypeError("%s.add_run takes the run's rows as a device tensor" % WHO)
-            if rows.dim() != 2 or rows.shape[1] != 4 or rows.dtype != torch.float32:
-                raise ValueError("%s.add_run: rows must be float32 [n,4]" % WHO)
-        n = 0 if rows is None else int(rows.shape[0])
-        if labels is not None:
-            if not torch.is_tensor(labels):
-                labels = torch.from_numpy(np.ascontiguousarray(np.asarray(labels)))
-            if labels.dtype != torch.bool or labels.dim() != 1 or int(labels.shape[0]) != n:
-                raise ValueError("%s.add_run: labels must be bool [%d]" % (WHO, n))
-        if covered is not None and covered != n:
-            raise ValueError("%s.add_run: counts sum to %d rows, the run has %d" % (WHO, covered, n))
-        if rows is not None and not rows.is_cuda:
-            raise TypeError("%s.add_run takes the run's rows as a device tensor" % WHO)
+        n, labels, bounds = _rowpasses.check_run(WHO, rows, counts, n_signal, labels, host_error=TypeError)
         st = self._dev()
         dev = self.device
         if n == 0:
-            zero, zero_bad = _rowpasses.no_rows(dev)
-            return {"n": zero, "n_bad": zero_bad, "mask": None if keep is None else torch.zeros((0,), dtype=torch.bool, device=dev)}
+            return _rowpasses.no_rows(dev, mask=True, keep=keep)
         rows = rows.to(dev).contiguous()
         lib = _capi.lib()
         stream = stream_ptr(dev)
-        H, W, F = self.height, self.width, self.n_settings
+        F = self.n_settings
         lengths_c, sigmas_c, supports_c = self._tables_c
-        lab = None if labels is None else labels.to(dev, non_blocking=True).to(torch.uint8).contiguous()
-        # (the table goes up without a wait: through pinned memory of torch's caching host allocator, which keeps it until the copy ran)
-        lb = None if bounds is None else torch.from_numpy(bounds).pin_memory().to(dev, non_blocking=True)
-        mask = None if keep is None else torch.empty((n,), dtype=torch.uint8, device=dev)
+        lab, lb = _rowpasses.labels_to_device(labels, bounds, dev)
+        mask = _rowpasses.new_mask(keep, n, dev)
         keep_li, keep_si, keep_ki = keep_at if keep_at is not None else (0, 0, 0)
-        cnt = torch.zeros((2,), dtype=torch.int64, device=dev)
         passed, totals, seen = st["counts"][:2 * F], st["counts"][2 * F:2 * F + 2], st["counts"][2 * F + 2:]
-        for r0 in range(0, n, self.max_rows_per_pass):
-            m = min(self.max_rows_per_pass, n - r0)
-            ev = rows[r0:r0 + m]
-            xy = torch.empty((1 + m,), dtype=torch.int32, device=dev)
-            idx = torch.empty((m,), dtype=torch.int32, device=dev)
+        run = _rowpasses.WindowPasses(self, rows, st["tail"], seen, keep=mask)
+        for r0, m, xy, idx, n_valid in run:
             row_lab = torch.empty((m,), dtype=torch.uint8, device=dev)
-            blk = torch.empty(((m + 255) // 256 + 1,), dtype=torch.int32, device=dev)  # (the last entry: the pass's valid rows)
-            n_valid = blk[-1:]
-            keep_ptr = None if mask is None else C.c_void_p(mask.data_ptr() + r0)
-            check(lib.v2e_window_compact(ptr(ev), m, H, W, ptr(st["tail"]), 1, ptr(xy), ptr(idx), ptr(blk), ptr(n_valid), ptr(cnt),
-                                         ptr(seen), keep_ptr, stream), "v2e_window_compact")
-            check(lib.v2e_dwindow_labels(ptr(idx), m, ptr(n_valid), None if lab is None else C.c_void_p(lab.data_ptr() + r0), ptr(lb),
-                                         0 if lb is None else int(lb.shape[0]), r0, ptr(row_lab), ptr(totals), stream),
-                  "v2e_dwindow_labels")
+            check(lib.v2e_dwindow_labels(ptr(idx), m, ptr(n_valid), *_rowpasses.label_args(lab, lb, r0), ptr(row_lab), ptr(totals),
+                                         stream), "v2e_dwindow_labels")
             check(lib.v2e_dwindow_sweep(ptr(xy), ptr(idx), ptr(row_lab), m, ptr(n_valid), lengths_c, len(self.lengths), sigmas_c,
                                         len(self.sigmas), supports_c, len(self.supports), ptr(st["rings"]), ptr(st["pos"]), ptr(passed),
-                                        keep_ptr, keep_li, keep_si, keep_ki, stream), "v2e_dwindow_sweep")
-            self.passes += 1
-        return {"n": cnt[0], "n_bad": cnt[1], "mask": None if mask is None else mask.view(torch.bool)}
+                                        run.keep_ptr(r0), keep_li, keep_si, keep_ki, stream), "v2e_dwindow_sweep")
+        return {"n": run.n, "n_bad": run.n_bad, "mask": None if mask is None else mask.view(torch.bool)}
 
     def result(self):
         """The counts so far as a DoubleWindowResult: one small read-back (it waits for the runs enqueued so far)."""

@@ -35,7 +35,6 @@ import torch
 from . import _capi, _rowpasses
 from ._capi import check, ptr, stream_ptr
 from ._rowpasses import DEFAULT_ROWS_PER_PASS
-from .denoise import label_bounds
 from .patches import MAX_RADIUS, frame_labels, roc_counts
 
 MAX_HIDDEN = 64
@@ -190,24 +189,7 @@ class MLPFilter(object):
                 raise ValueError("MLPFilter.add_run: keep must be a float threshold, got %r" % (keep,)) from None
             if math.isnan(keep):
                 raise ValueError("MLPFilter.add_run: keep must not be NaN")
-        if labels is not None and n_signal is not None:
-            raise ValueError("MLPFilter.add_run: labels or n_signal, not both")
-        if n_signal is not None and counts is None:
-            raise ValueError("MLPFilter.add_run: n_signal needs the run's counts")
-        covered = None
-        if n_signal is not None:
-            covered = label_bounds(counts, n_signal)[1]
-        if rows is not None:
-            if not torch.is_tensor(rows) or rows.dim() != 2 or rows.shape[1] != 4 or rows.dtype != torch.float32 or not rows.is_cuda:
-                raise ValueError("MLPFilter.add_run: rows must be a device float32 [n,4] tensor")
-        n = 0 if rows is None else int(rows.shape[0])
-        if labels is not None:
-            if not torch.is_tensor(labels):
-                labels = torch.from_numpy(np.ascontiguousarray(np.asarray(labels)))
-            if labels.dtype != torch.bool or labels.dim() != 1 or int(labels.shape[0]) != n:
-                raise ValueError("MLPFilter.add_run: labels must be bool [%d]" % n)
-        if covered is not None and covered != n:
-            raise ValueError("MLPFilter.add_run: counts sum to %d rows, the run has %d" % (covered, n))
+        n, labels, _ = _rowpasses.check_run("MLPFilter", rows, counts, n_signal, labels)
         if out is not None:
             if not torch.is_tensor(out) or out.dtype != torch.float32 or not out.is_cuda or out.dim() != 1 or int(out.shape[0]) < n or \
                     not out.is_contiguous():
@@ -217,17 +199,15 @@ class MLPFilter(object):
         st = self._dev()
         dev = self.device
         if n == 0:
-            zero, zero_bad = _rowpasses.no_rows(dev)
-            empty = torch.zeros((0,), dtype=torch.bool, device=dev)
-            return {"scores": out[:0] if out is not None else torch.empty((0,), dtype=torch.float32, device=dev), "valid": empty,
-                    "mask": None if keep is None else empty.clone(), "n": zero, "n_bad": zero_bad}
+            return dict(_rowpasses.no_rows(dev, mask=True, keep=keep), valid=torch.zeros((0,), dtype=torch.bool, device=dev),
+                        scores=out[:0] if out is not None else torch.empty((0,), dtype=torch.float32, device=dev))
         rows = rows.to(dev).contiguous()
         lib = _capi.lib()
         stream = stream_ptr(dev)
         H, W = self.height, self.width
         scores = out[:n] if out is not None else torch.empty((n,), dtype=torch.float32, device=dev)
         valid = torch.empty((n,), dtype=torch.uint8, device=dev)
-        mask = None if keep is None else torch.empty((n,), dtype=torch.uint8, device=dev)
+        mask = _rowpasses.new_mask(keep, n, dev)
         run = _rowpasses.RowPasses(self, rows, st["seg"])
         for r0, m, ev, skeys in run:
             check(lib.v2e_patches_mlp_scores(ptr(ev), m, H, W, ptr(skeys), ptr(st["seg"]), ptr(st["last_t"]), ptr(st["last_p"]),

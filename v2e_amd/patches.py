@@ -38,8 +38,7 @@ import torch
 
 from . import _capi, _rowpasses
 from ._capi import check, ptr, stream_ptr
-from ._rowpasses import DEFAULT_ROWS_PER_PASS
-from .denoise import label_bounds
+from ._rowpasses import DEFAULT_ROWS_PER_PASS, label_bounds
 
 MODES = {"age": 0, "linear": 1}
 MAX_RADIUS = 3
@@ -110,10 +109,7 @@ class EventPatches(object):
         0-dim int64 (reading one waits for the device; the call does not)."""
         # every ValueError before the library or the device is touched
         P = self.size
-        if rows is not None:
-            if not torch.is_tensor(rows) or rows.dim() != 2 or rows.shape[1] != 4 or rows.dtype != torch.float32 or not rows.is_cuda:
-                raise ValueError("EventPatches.add_run: rows must be a device float32 [n,4] tensor")
-        n = 0 if rows is None else int(rows.shape[0])
+        n = _rowpasses.check_run("EventPatches", rows)[0]
         if out is not None:
             if not torch.is_tensor(out) or out.dtype != torch.float32 or not out.is_cuda or out.dim() != 4 or \
                     tuple(out.shape[1:]) != (2, P, P) or int(out.shape[0]) < n or not out.is_contiguous():
@@ -126,9 +122,8 @@ class EventPatches(object):
         st = self._dev()
         dev = self.device
         if n == 0:
-            zero, zero_bad = _rowpasses.no_rows(dev)
             feats = out[:0] if out is not None else torch.empty((0, 2, P, P), dtype=torch.float32, device=dev)
-            return {"features": feats, "valid": torch.zeros((0,), dtype=torch.bool, device=dev), "n": zero, "n_bad": zero_bad}
+            return dict(_rowpasses.no_rows(dev), features=feats, valid=torch.zeros((0,), dtype=torch.bool, device=dev))
         rows = rows.to(dev).contiguous()
         lib = _capi.lib()
         stream = stream_ptr(dev)

@@ -36,7 +36,6 @@ gives identical integers and identical final maps.  `add_run` fits the `on_event
 `SyntheticToEvents.run`, the chunks of `EventFileReader` and `generate_events_batch(return_device=True)`; it enqueues on the current
 stream and never waits for the device.  `result()` is the one read-back.
 """
-import ctypes as C
 import math
 
 import numpy as np
@@ -45,7 +44,6 @@ import torch
 from . import _capi, _rowpasses
 from ._capi import check, ptr, stream_ptr
 from ._rowpasses import DEFAULT_ROWS_PER_PASS
-from .denoise import label_bounds
 
 MAX_EDGES = 256
 MAX_TIME_BINS = 1 << 20
@@ -257,10 +255,6 @@ class EventStats(object):
             self._state["sums"].copy_(self._state["init"])
         return self._state
 
-    def _upload(self, a):
-        """A small host table to the device without waiting for it (pinned memory of torch's caching host allocator)."""
-        return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(self.device, non_blocking=True)
-
     def reset(self):
         """The next stream: the maps back to -inf / 0, every sum to zero (enqueued on the current stream)."""
         if self._state is not None:
@@ -289,43 +283,23 @@ class EventStats(object):
         Returns {"n": valid rows, "n_bad": bad rows}: 0-dim int64 device tensors (reading one waits for the device; the call does
         not)."""
         # every ValueError before the library or the device is touched
-        if labels is not None and n_signal is not None:
-            raise ValueError("EventStats.add_run: labels or n_signal, not both")
-        if n_signal is not None and counts is None:
-            raise ValueError("EventStats.add_run: n_signal needs the run's counts")
-        bounds = covered = None
-        if n_signal is not None:
-            bounds, covered = label_bounds(counts, n_signal)
-        if rows is not None:
-            if not torch.is_tensor(rows) or rows.dim() != 2 or rows.shape[1] != 4 or rows.dtype != torch.float32 or not rows.is_cuda:
-                raise ValueError("EventStats.add_run: rows must be a device float32 [n,4] tensor")
-        n = 0 if rows is None else int(rows.shape[0])
-        if labels is not None:
-            if not torch.is_tensor(labels):
-                labels = torch.from_numpy(np.ascontiguousarray(np.asarray(labels)))
-            if labels.dtype != torch.bool or labels.dim() != 1 or int(labels.shape[0]) != n:
-                raise ValueError("EventStats.add_run: labels must be bool [%d]" % n)
-        if covered is not None and covered != n:
-            raise ValueError("EventStats.add_run: counts sum to %d rows, the run has %d" % (covered, n))
+        n, labels, bounds = _rowpasses.check_run("EventStats", rows, counts, n_signal, labels)
         st = self._dev()
         dev = self.device
         if n == 0:
-            zero, zero_bad = _rowpasses.no_rows(dev)
-            return {"n": zero, "n_bad": zero_bad}
+            return _rowpasses.no_rows(dev)
         rows = rows.to(dev).contiguous()
         lib = _capi.lib()
         stream = stream_ptr(dev)
         H, W = self.height, self.width
         (x0, x1), (y0, y1) = self.roi
-        lab = None if labels is None else labels.to(dev, non_blocking=True).to(torch.uint8).contiguous()
-        lb = None if bounds is None or len(bounds) == 0 else self._upload(bounds)
+        lab, lb = _rowpasses.labels_to_device(labels, bounds, dev)
         K = 0 if st["bounds"] is None else int(st["bounds"].shape[0]) - 1
         run = _rowpasses.RowPasses(self, rows, st["seg"])
         for r0, m, ev, skeys in run:
             check(lib.v2e_stats_rows(ptr(ev), m, H, W, ptr(skeys), ptr(st["seg"]), ptr(st["last_t"]), ptr(st["last_p"]), x0, x1, y0, y1,
                                      ptr(st["edges"]), len(self.isi_edges), ptr(st["bounds"]), K,
-                                     None if lab is None else C.c_void_p(lab.data_ptr() + r0), ptr(lb),
-                                     0 if lb is None else int(lb.shape[0]), r0, ptr(st["count"]), ptr(st["isi_hist"]), ISI_REPLICAS,
+                                     *_rowpasses.label_args(lab, lb, r0), ptr(st["count"]), ptr(st["isi_hist"]), ISI_REPLICAS,
                                      ptr(st["time_hist"]) if K else None, self._time_replicas(), ptr(st["sums"]), stream),
                   "v2e_stats_rows")
             check(lib.v2e_stats_map_update(ptr(ev), ptr(skeys), ptr(st["seg"]), H, W, ptr(st["last_t"]), ptr(st["last_p"]), stream),

@@ -32,8 +32,8 @@ import torch
 
 from . import _capi, _rowpasses
 from ._capi import check, ptr, stream_ptr
+from ._roc import RocResult
 from ._rowpasses import DEFAULT_ROWS_PER_PASS
-from .denoise import label_bounds
 
 MAX_LENGTHS = 64
 MAX_LENGTH = 1024
@@ -44,7 +44,8 @@ MAX_SIDE = 65535
 XY_NONE = 0xFFFFFFFF  # the packed word of "no row yet"
 
 
-def _int_table(name, table, most, lo, hi, who="WindowSweep"):
+def int_table(who, name, table, most, lo, hi):
+    """`table` as an ascending int64 table of 1 .. most integers in lo .. hi; ValueError in the words of class `who`."""
     try:
         t = np.array(table, dtype=np.float64).reshape(-1)
     except (TypeError, ValueError):
@@ -56,7 +57,8 @@ def _int_table(name, table, most, lo, hi, who="WindowSweep"):
     return t.astype(np.int64)
 
 
-def _check_keep(keep, lmax, who="WindowSweep"):
+def check_keep(who, keep, lmax):
+    """keep = (L, sigma, k) of `who`.add_run as three ints, L in 1 .. lmax; None stays None."""
     if keep is None:
         return None
     try:
@@ -75,7 +77,7 @@ def _check_keep(keep, lmax, who="WindowSweep"):
     return ints
 
 
-class WindowResult(object):
+class WindowResult(RocResult):
     """The histogram of a `WindowSweep` on the host, and the ROC it holds.
 
     hist      int64 [4,S,2,NL+1]: hist[k-1, s, label, b] rows whose depth d[s][k] falls in bin b (label 1 = signal, 0 = noise)
@@ -101,28 +103,11 @@ class WindowResult(object):
     def passed(self):
         return np.cumsum(self.hist[:, :, :, :-1], axis=3)
 
-    def _rate(self, label, n):
-        p = self.passed[:, :, label, :].astype(np.float64)
-        return p / n if n > 0 else np.full(p.shape, np.nan)
-
-    @property
-    def tpr(self):
-        return self._rate(1, self.n_signal)
-
-    @property
-    def fpr(self):
-        return self._rate(0, self.n_noise)
-
     def best(self):
         """(L, sigma, k, tpr, fpr) at the first maximum of tpr - fpr, taken in (k ascending, sigma ascending, L ascending) order.
         ValueError when there is no signal or no noise row (tpr - fpr is NaN everywhere)."""
-        tpr, fpr = self.tpr, self.fpr
-        d = (tpr - fpr).reshape(-1)
-        if np.all(np.isnan(d)):
-            raise ValueError("WindowResult.best: needs at least one signal and one noise row")
-        j = int(np.nanargmax(d))  # (the first maximum in C order)
-        k, s, b = np.unravel_index(j, tpr.shape)
-        return int(self.lengths[b]), int(self.sigmas[s]), int(k) + 1, float(tpr[k, s, b]), float(fpr[k, s, b])
+        (k, s, b), tpr, fpr = self._best("WindowResult")
+        return int(self.lengths[b]), int(self.sigmas[s]), int(k) + 1, tpr, fpr
 
 
 class WindowSweep(object):
@@ -133,8 +118,8 @@ class WindowSweep(object):
         self.height, self.width = int(height), int(width)
         if not (1 <= self.height <= MAX_SIDE and 1 <= self.width <= MAX_SIDE):  # (no per-pixel map: no limit on height * width)
             raise ValueError("WindowSweep: height and width must be in 1 .. %d" % MAX_SIDE)
-        self.lengths = _int_table("lengths", lengths, MAX_LENGTHS, 1, MAX_LENGTH)
-        self.sigmas = _int_table("sigmas", sigmas, MAX_SIGMAS, 0, MAX_SIGMA)
+        self.lengths = int_table("WindowSweep", "lengths", lengths, MAX_LENGTHS, 1, MAX_LENGTH)
+        self.sigmas = int_table("WindowSweep", "sigmas", sigmas, MAX_SIGMAS, 0, MAX_SIGMA)
         self.max_length = int(self.lengths[-1])
         self.max_rows_per_pass = _rowpasses.check_rows_per_pass("WindowSweep", max_rows_per_pass)
         self.device = torch.device(device)
@@ -180,62 +165,27 @@ class WindowSweep(object):
         Returns {"n": valid rows, "n_bad": bad rows, "mask": bool [n] or None}: n and n_bad are 0-dim int64 device tensors (reading
         one waits for the device; the call does not), mask a device tensor in the rows' order."""
         # every ValueError before the library or the device is touched
-        keep = _check_keep(keep, self.max_length)
-        if labels is not None and n_signal is not None:
-            raise ValueError("WindowSweep.add_run: labels or n_signal, not both")
-        if n_signal is not None and counts is None:
-            raise ValueError("WindowSweep.add_run: n_signal needs the run's counts")
-        bounds = covered = None
-        if n_signal is not None:
-            bounds, covered = label_bounds(counts, n_signal)
-        if rows is not None:
-            if not torch.is_tensor(rows):
-                raise TypeError("WindowSweep.add_run takes the run's rows as a device tensor")
-            if rows.dim() != 2 or rows.shape[1] != 4 or rows.dtype != torch.float32:
-                raise ValueError("WindowSweep.add_run: rows must be float32 [n,4]")
-        n = 0 if rows is None else int(rows.shape[0])
-        if labels is not None:
-            if not torch.is_tensor(labels):
-                labels = torch.from_numpy(np.ascontiguousarray(np.asarray(labels)))
-            if labels.dtype != torch.bool or labels.dim() != 1 or int(labels.shape[0]) != n:
-                raise ValueError("WindowSweep.add_run: labels must be bool [%d]" % n)
-        if covered is not None and covered != n:
-            raise ValueError("WindowSweep.add_run: counts sum to %d rows, the run has %d" % (covered, n))
-        if rows is not None and not rows.is_cuda:
-            raise TypeError("WindowSweep.add_run takes the run's rows as a device tensor")
+        keep = check_keep("WindowSweep", keep, self.max_length)
+        n, labels, bounds = _rowpasses.check_run("WindowSweep", rows, counts, n_signal, labels, host_error=TypeError)
         st = self._dev()
         dev = self.device
         if n == 0:
-            zero, zero_bad = _rowpasses.no_rows(dev)
-            return {"n": zero, "n_bad": zero_bad, "mask": None if keep is None else torch.zeros((0,), dtype=torch.bool, device=dev)}
+            return _rowpasses.no_rows(dev, mask=True, keep=keep)
         rows = rows.to(dev).contiguous()
         lib = _capi.lib()
         stream = stream_ptr(dev)
-        H, W, NL, S, lmax = self.height, self.width, len(self.lengths), len(self.sigmas), self.max_length
-        lab = None if labels is None else labels.to(dev, non_blocking=True).to(torch.uint8).contiguous()
-        # (the table goes up without a wait: through pinned memory of torch's caching host allocator, which keeps it until the copy ran)
-        lb = None if bounds is None else torch.from_numpy(bounds).pin_memory().to(dev, non_blocking=True)
-        mask = None if keep is None else torch.empty((n,), dtype=torch.uint8, device=dev)
+        NL, S, lmax = len(self.lengths), len(self.sigmas), self.max_length
+        lab, lb = _rowpasses.labels_to_device(labels, bounds, dev)
+        mask = _rowpasses.new_mask(keep, n, dev)
         keep_l, keep_sigma, keep_k = keep if keep is not None else (1, 0, 1)
         keep_sigma = min(keep_sigma, 1 << 31)  # (beyond every distance of a sensor: the same filter)
-        cnt = torch.zeros((2,), dtype=torch.int64, device=dev)
-        for r0 in range(0, n, self.max_rows_per_pass):
-            m = min(self.max_rows_per_pass, n - r0)
-            ev = rows[r0:r0 + m]
-            xy = torch.empty((lmax + m,), dtype=torch.int32, device=dev)
-            idx = torch.empty((m,), dtype=torch.int32, device=dev)
-            blk = torch.empty(((m + 255) // 256 + 1,), dtype=torch.int32, device=dev)  # (the last entry: the pass's valid rows)
-            n_valid = blk[-1:]
-            keep_ptr = None if mask is None else C.c_void_p(mask.data_ptr() + r0)
-            check(lib.v2e_window_compact(ptr(ev), m, H, W, ptr(st["tail"]), lmax, ptr(xy), ptr(idx), ptr(blk), ptr(n_valid), ptr(cnt),
-                                         ptr(st["seen"]), keep_ptr, stream), "v2e_window_compact")
+        run = _rowpasses.WindowPasses(self, rows, st["tail"], st["seen"], keep=mask)
+        for r0, m, xy, idx, n_valid in run:
             check(lib.v2e_window_depths(ptr(xy), ptr(idx), m, ptr(n_valid), ptr(st["lengths"]), NL, lmax, self._sigmas_c, S,
-                                        None if lab is None else C.c_void_p(lab.data_ptr() + r0), ptr(lb),
-                                        0 if lb is None else int(lb.shape[0]), r0, ptr(st["hist"]), keep_ptr, keep_l, keep_sigma, keep_k,
-                                        stream), "v2e_window_depths")
+                                        *_rowpasses.label_args(lab, lb, r0), ptr(st["hist"]), run.keep_ptr(r0), keep_l, keep_sigma,
+                                        keep_k, stream), "v2e_window_depths")
             check(lib.v2e_window_tail(ptr(xy), ptr(n_valid), m, lmax, ptr(st["tail"]), stream), "v2e_window_tail")
-            self.passes += 1
-        return {"n": cnt[0], "n_bad": cnt[1], "mask": None if mask is None else mask.view(torch.bool)}
+        return {"n": run.n, "n_bad": run.n_bad, "mask": None if mask is None else mask.view(torch.bool)}
 
     def result(self):
         """The histogram so far as a WindowResult: one small read-back (it waits for the runs enqueued so far)."""
